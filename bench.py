@@ -6,15 +6,25 @@ float32 tensors everywhere; conv1 of dense_e2 / e3 forward on three-way-split bf
 GEMMs of the dense blocks on two-way-split bf16 MFMAs ("bf16x3", ~5e-6 of a gradient's maximum), everything else on the
 exact-f32 MFMA.  `--forward-split 0 --backward-precision f32` = exact-f32 MFMA everywhere.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL).
 
+A plain run sets up, runs W warm-up steps and K timed steps, and prints the line: `value` and `ms_per_step` are the K timed
+steps.  `--dump-outputs DIR` then writes what the last timed step computed (loss, its components and predictions, seeded
+samples of the updated parameters, their gradients and the BatchNorm buffers) as DIR/<name>.npy, float32 or float64, at most
+DUMP_LIMIT bytes; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+The optimiser runs at lr 0 (bench_train says why), so every step starts from the seeded parameters and only the BatchNorm
+running statistics in the dump depend on the step count.  Two runs still differ in the last bits (the default path reduces split-K partials with float atomics; measured
+on MI355X: loss and depth bit-identical, ordinal probabilities within 4e-6, gradient correlation 0.999997).
+
 One JSON line on rank 0 (< 4 KB: the driver's record keeps a bounded tail of stdout; tests/test_bench_line.py holds the
-size), with
+size).  With --full it also carries
   roofline     - the DOMINANT kernel by summed duration: FLOPs it executes on its matrix pipe / its average launch
                  duration measured with HIP events on its launch stream, against that pipe's dense peak
   cpu_baseline - the oracle (CPU restatement of the reference, oracle/) timed on the host cores on a
-                 bounded sample (batch-16 full train steps incl. AdamW) - a reported baseline, never the thing shipped.
+                 bounded sample (batch-16 full train steps incl. AdamW) - a reported baseline, never the thing shipped,
+and, at N = 1 on the headline geometry, one summary row per extra configuration (BASELINE configs[1] and [4], the mixed-precision
+modes), and the communication timings of config.comm; each of these runs steps of its own after the timed region.
 Everything else that used to ride on the line (per-kernel table, the other BASELINE configs in full, the prose on the
 arithmetic) goes to DETAIL_FILE next to this script; the line names it.
 """
@@ -60,8 +70,15 @@ def main():
     ap.add_argument("--gemm-bf16", type=int, default=0, choices=[0, 1, 2, 3],
                     help="MIXED-PRECISION arithmetic (the reference's default --precision 16): the GEMMs the two options above route to the split kernels round their operands to bf16, "
                     "one MFMA per product. 1: forward and gradient GEMMs, 2: forward only, 3: gradient GEMMs only. NOT the parity configuration - a separately labelled line, never the headline")
-    ap.add_argument("--no-extra-configs", action="store_true", help="headline line only (skip BASELINE configs[1] and configs[4] at N=1)")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full: headline line only (skip BASELINE configs[1] and configs[4] at N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baseline, roofline leg, communication timings, extra configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:                                        # a plain run: the timed steps and the line, nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_extra_configs = True
     if args.workload == "fwd_bf16":
         line = bench_fwd_bf16(args)
         if line is not None:
@@ -81,7 +98,7 @@ def main():
             torch.cuda.empty_cache()
         extra = []
         release()
-        a2 = argparse.Namespace(**vars(args))
+        a2 = argparse.Namespace(**dict(vars(args), dump_outputs=None))     # the dump is the headline's
         a2.batch, a2.no_cpu_baseline, a2.steps, a2.warmup = 8, True, max(args.steps, 10), max(args.warmup, 2)
         def guarded(fn, *a, **kw):                           # a failing extra configuration must not cost the headline its line
             try:
@@ -92,14 +109,14 @@ def main():
                 extra.append({"metric": kw.get("metric", getattr(fn, "__name__", "?")), "value": None, "unit": "images/s", "ms_per_step": None, "dtype": "FAILED: " + repr(exc)[:80]})
         guarded(bench_fwd_bf16, a2)
         release()
-        a3 = argparse.Namespace(**vars(args))
+        a3 = argparse.Namespace(**dict(vars(args), dump_outputs=None))
         a3.steps, a3.warmup = min(args.steps, 5), min(args.warmup, 2)
         guarded(bench_train, a3, 8, 352, 1216, with_cpu_baseline=False, metric="depth-maps/sec KITTI 352x1216 batch=8 fwd+bwd")
         if not args.gemm_bf16:
             # the headline geometry once more in the mixed-precision arithmetic mode (reference default --precision 16, train.py:11,57-58)
             release()
             for mode, what in ((1, "bf16 operands: fwd + gradient GEMMs"), (3, "bf16 operands: gradient GEMMs only")):
-                a4 = argparse.Namespace(**vars(args))
+                a4 = argparse.Namespace(**dict(vars(args), dump_outputs=None))
                 a4.gemm_bf16 = mode
                 guarded(bench_train, a4, 16, 228, 304, with_cpu_baseline=False, metric=f"depth-maps/sec NYU 228x304 batch=16 fwd+bwd, mixed precision ({what})")
                 release()
@@ -188,6 +205,66 @@ def emit(full):
     return line
 
 
+DUMP_LIMIT = 64 * 2**20                # bytes of all --dump-outputs arrays together
+SAMPLE = 1 << 21                       # elements kept of a flattened output larger than this (fixed, seeded indices)
+
+
+def tensor_arrays(name, obj):
+    """{name: float array} for a tensor, or for every tensor of a (nested) list / tuple / dict as name_<index or key>.  Floating
+    tensors keep float64 or become float32 (bf16 / f16 widen exactly); integer and boolean ones become float64 (exact)."""
+    if isinstance(obj, torch.Tensor):
+        t = obj.detach()
+        t = t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()
+        return {name: t.reshape(-1).cpu().numpy() if t.dim() == 0 else t.cpu().numpy()}     # a scalar as shape (1,)
+    if isinstance(obj, (list, tuple)):
+        obj = dict(enumerate(obj))
+    if isinstance(obj, dict):
+        out = {}
+        for k, v in obj.items():
+            out.update(tensor_arrays(f"{name}_{k}", v))
+        return out
+    return {}
+
+
+def flat_sample(tensors, seed):
+    """The tensors flattened and concatenated (in order), or SAMPLE elements of that at sorted indices drawn from `seed` when it
+    is longer: the same positions in every run of the same model."""
+    import numpy as np
+    dt = torch.float32 if all(t.dtype == torch.float32 for t in tensors) else torch.float64
+    flat = torch.cat([t.detach().reshape(-1).to(dt) for t in tensors])
+    if flat.numel() > SAMPLE:
+        idx = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), SAMPLE))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def train_step_outputs(model, loss, parts):
+    """What a caller of the training step receives from one step: the loss and the components / predictions training_step
+    returns, and the model it updated - parameters after AdamW, their gradients (zeros where a parameter receives none) and the
+    BatchNorm buffers (running statistics, step counters)."""
+    ps = list(model.parameters())
+    out = tensor_arrays("loss", loss)
+    out.update(tensor_arrays("step", parts))
+    out["params"] = flat_sample(ps, seed=0)
+    out["grads"] = flat_sample([p.grad if p.grad is not None else torch.zeros_like(p) for p in ps], seed=0)
+    out["buffers"] = flat_sample(list(model.buffers()), seed=1)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy (float32 or float64 only); the whole set must stay within DUMP_LIMIT bytes."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, f"outputs are {total} bytes, more than {DUMP_LIMIT}"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return total
+
+
 def host_threads():
     """Threads the CPU baseline may use = what the box really gives this process: the affinity mask, capped by the cgroup CPU quota
     when one is set (a quota of 16 cores under a 64-core mask makes 64 threads SLOWER than 16), overridable with RDM_CPU_THREADS."""
@@ -260,17 +337,21 @@ def bench_train(args, B, H, W, with_cpu_baseline, metric="depth-maps/sec NYU 228
     xg, yg = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
     model.flatten_parameters()
     sync = parallel.attach(model, exchange=args.exchange)
-    opt = harness.FusedAdamW(model, lr=1e-4)
+    # lr 0: every step does AdamW's full work (both moments, the decoupled decay, every parameter read and written back) but leaves
+    # the parameters where the seed put them, so each step computes the same step from the same state.  At the reference's 1e-4 the
+    # one synthetic batch, repeated, drives the fine details of the decomposition tail to NaN after ~43 steps on MI355X (loss NaN from
+    # there on, conv-stack gradients still finite): the line's loss, the dumped outputs and the work timed would depend on the step count.
+    opt = harness.FusedAdamW(model, lr=0.0)
 
     def step():
         opt.zero_grad()
-        loss, _ = harness.training_step(model, xg, yg)
+        loss, parts = harness.training_step(model, xg, yg)
         loss.backward()
         if world > 1:
             opt.step(sync=sync)                               # per bucket: stage k's AdamW as its reduction lands
         else:
             opt.step(grad_scale=sync.finish())
-        return loss
+        return loss, parts
 
     def note(msg):
         if rank == 0:
@@ -287,12 +368,15 @@ def bench_train(args, B, H, W, with_cpu_baseline, metric="depth-maps/sec NYU 228
     launches0 = L.rdm_launch_count()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, parts = step()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     lib_launches_per_step = (L.rdm_launch_count() - launches0) / args.steps
+    if args.dump_outputs and rank == 0:                   # before any further step overwrites the workspace or the parameters
+        dump_outputs(args.dump_outputs, train_step_outputs(model, loss, parts))
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     if not args.no_roofline:
         # roofline leg: the SAME K steps again, immediately after the timed region, with a HIP event pair
         # recorded around every conv launch (the events cost ~3.5 us each between dependent kernels,
@@ -382,7 +466,7 @@ def bench_train(args, B, H, W, with_cpu_baseline, metric="depth-maps/sec NYU 228
     comm = {"allreduce_bytes_per_step": sync.bytes_per_step() if world > 1 else 0, "stages": len(sync.slices),
             "exchange": "one asynchronous RCCL all-reduce (sum) per backward stage on the flat gradient buffer, last layers first; AdamW applies 1/N",
             "exchange_short": sync.exchange if world > 1 else "none (N=1)", "optimizer": getattr(opt, "mode", "after the last stage")}
-    if world > 1:
+    if world > 1 and args.full:
         sync.timing = True
         for _ in range(min(args.steps, 3)):
             step()
@@ -390,7 +474,7 @@ def bench_train(args, B, H, W, with_cpu_baseline, metric="depth-maps/sec NYU 228
         comm["exposed_wait_basis"] = "device events around GradSync.finish(): compute stream idle until the last reduction has landed"
         comm["side_stream_join"] = "after every backward stage (the exchange consumes gradients stage by stage)"
         sync.timing = False
-    elif not args.no_roofline:
+    elif world == 1 and not args.no_roofline:
         # N = 1: the cost of joining the weight-gradient stream after each of the 13 stages (what N > 1 pays) instead of once per segment
         hook = model.grad_ready_hook
         model.grad_ready_hook = (lambda stage: None) if hook is None or world == 1 else hook
@@ -483,20 +567,22 @@ def bench_fwd_bf16(args):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # conv-stack-only time (the tail is ~10 small launches): same K steps of the native forward alone
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        with torch.no_grad():
-            model._native_forward_bf16(xg)
-    torch.cuda.synchronize()
-    stack_ms = (time.perf_counter() - t1) / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tensor_arrays("out", out))
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     roof = None
     if not args.no_roofline:
+        # conv-stack-only time (the tail is ~10 small launches): same K steps of the native forward alone
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            with torch.no_grad():
+                model._native_forward_bf16(xg)
+        torch.cuda.synchronize()
+        stack_ms = (time.perf_counter() - t1) / args.steps * 1e3
         L.rdm_profile_enable(1)
         for _ in range(args.steps):
             with torch.no_grad():

@@ -125,7 +125,8 @@ def test_bench_two_ranks_prints_one_weak_scaling_json_line():
     env = dict(os.environ)
     env.pop("HSA_ENABLE_IPC_MODE_LEGACY", None)          # bench.py sets the dmabuf IPC mode itself (first lines of the file), before any HIP call
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--backend", backend]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--backend", backend,
+           "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
