@@ -397,6 +397,50 @@ double rdm_net_bf16_forward_bytes(const rdm_net* net);
 int rdm_net_bf16_prepare(rdm_net* net, void* const* tensors, void* wbuf, size_t wbuf_bytes, rdm_stream_t stream);
 int rdm_net_forward_bf16(rdm_net* net, const float* x_nchw, void* const* tensors, const void* wbuf, size_t wbuf_bytes, void* workspace,
                          size_t workspace_bytes, float* logits_nchw, rdm_stream_t stream);
+/* The encoder output (trans_e4, RDM_Net.py:94) of the last rdm_net_forward_bf16 on `workspace`: B*h*w rows of 1056 bf16 (NHWC) copied
+ * into `out` with row stride `ldo` (>= 1056 elements) - e.g. the first channels of a relative decoder's block buffer.  The bf16 twin of
+ * rdm_net_encoder_output. */
+int rdm_net_encoder_output_bf16(const rdm_net* net, const void* workspace, size_t workspace_bytes, void* out, int32_t ldo, rdm_stream_t stream);
+
+/* The relative decoders d_6..d_10 (RDM_Net.py:57-61,106-125; Decoder :137-162, WSMLayer :163-236) on the bf16 inference path
+ * (csrc/wsm_bf16.hip): dense block (the kernels of rdm_net_forward_bf16, eval-mode BatchNorm folded once by the prepare call) -> WSM chain
+ * (every conv on one bf16 implicit-GEMM kernel family, f32 accumulation, each layer's output written once in the reference's cat order,
+ * :234) -> conv1 (:156-157).  `id` is 6..10.
+ *   rdm_rel_num_tensors          number of tensors of decoder `id` (its state_dict: dense_layer.*, wsm_block.*, conv1.*, conv2.*, in order)
+ *   rdm_rel_bf16_weight_bytes    size of the prepared-weight buffer (independent of the batch)
+ *   rdm_rel_bf16_prepare         `tensors` = the decoder's state_dict tensors in order (f32 device pointers); bf16 weights packed once,
+ *                                BatchNorm folded to eval-mode (scale, shift); call again after any weight or running-statistics change.
+ *   rdm_rel_bf16_workspace_bytes activation workspace of one forward at `batch` (256-byte aligned, caller-owned)
+ *   rdm_rel_forward_bf16         enc: (B*8*8, ld_enc) bf16 NHWC, the 1056-channel trans_e4 output (rdm_net_encoder_output_bf16 or
+ *                                rdm_rel_bf16_input_nchw) -> out_map (B,1,S,S) f32, S = 2^(id-3): the map the relative head consumes.
+ *   rdm_rel_bf16_input_nchw      x (B,1056,8,8) f32 NCHW -> enc (B*64, ld_enc) bf16 NHWC (standalone use of a decoder) */
+int rdm_rel_num_tensors(int32_t id);
+size_t rdm_rel_bf16_weight_bytes(int32_t id);
+int rdm_rel_bf16_prepare(int32_t id, void* const* tensors, void* wbuf, size_t wbuf_bytes, rdm_stream_t stream);
+size_t rdm_rel_bf16_workspace_bytes(int32_t id, int32_t batch);
+int rdm_rel_forward_bf16(int32_t id, const void* enc, int32_t ld_enc, int32_t batch, const void* wbuf, void* workspace, size_t workspace_bytes,
+                         float* out_map, rdm_stream_t stream);
+int rdm_rel_bf16_input_nchw(const float* x_nchw, int32_t batch, void* enc, int32_t ld_enc, rdm_stream_t stream);
+/* The WSM conv kernel's epilogue modes as operators (RDM_Net.py:163-236; the decoder forward above enqueues the same launches).  x: NHWC
+ * bf16 (B,h,w, ldx), channels [xoff, xoff + cin); w: bf16 [rows][K] with K = taps * pad32(cin), k = tap * pad32(cin) + ci (zero padded),
+ * rows allocated up to a multiple of 64; bias f32 (optional).  16-byte aligned operands; ldx, xoff multiples of 8.
+ *   rdm_wsm_conv_bf16    kxk (k = 1, 3, 5) stride 1, pad k/2, n outputs + bias -> bf16 channels [coff, coff + n) of out (B,h,w, ldc):
+ *                        input_adjustment_layer, conv1_1..conv1_5, conv2_1, conv2_2 (:202-212)
+ *   rdm_wsm_deconv_bf16  ConvTranspose2d(k2, s2) (:199) as a 1x1 to rows r = (2 i + j) * pad32(c) + co (bias in the same row order),
+ *                        stored through the pixel shuffle: out (B,2h,2w, ldc) bf16 channels [0, c), pixel (2y+i, 2x+j)
+ *   rdm_wsm_strip_bf16   the WSM strip convs on a (B,s,s) map, cin = the padded channel width (multiple of 32), K = 3 * s * cin:
+ *                        columns = 0: wsm_wx3 (3,s)/(1,s) after ZeroPad2d((0,0,1,1)), k = (dy * s + x) * cin + ci, one value per row repeated
+ *                        along W; columns = 1: wsm_3xh (s,3)/(s,1) after ZeroPad2d((1,1,0,0)), k = (dx * s + y) * cin + ci, one value per
+ *                        column repeated along H (:213-224) -> bf16 channels [coff, coff + n) of out (B,s,s, ldc)
+ *   rdm_wsm_conv1x1_f32  Decoder.conv1 (:156-157): 1x1 -> ONE channel + bias, f32 out (B*h*w) */
+int rdm_wsm_conv_bf16(const void* x, int32_t ldx, int32_t xoff, int32_t cin, const void* w, const float* bias, int32_t n, void* out, int32_t ldc, int32_t coff,
+                      int32_t batch, int32_t h, int32_t w_, int32_t k, rdm_stream_t stream);
+int rdm_wsm_deconv_bf16(const void* x, int32_t ldx, int32_t cin, const void* w, const float* bias, int32_t c, void* out, int32_t ldc, int32_t batch, int32_t h,
+                        int32_t w_, rdm_stream_t stream);
+int rdm_wsm_strip_bf16(const void* x, int32_t ldx, int32_t xoff, int32_t cin, const void* w, const float* bias, int32_t n, void* out, int32_t ldc, int32_t coff,
+                       int32_t batch, int32_t s, int32_t columns, rdm_stream_t stream);
+int rdm_wsm_conv1x1_f32(const void* x, int32_t ldx, int32_t cin, const void* w, const float* bias, float* out, int32_t batch, int32_t h, int32_t w_,
+                        rdm_stream_t stream);
 
 /* Backward in up to 4 segments so the caller can start reducing a segment's gradients (RCCL)
  * while the next one computes: 0 = decoder d_1, 1 = dense_e4+trans_e4, 2 = dense_e3+trans_e3,

@@ -90,6 +90,17 @@ _SIGNATURES = {
     "rdm_net_bf16_forward_bytes": (f64, [vp]),
     "rdm_net_bf16_prepare": (C.c_int, [vp, C.POINTER(vp), vp, sz, vp]),
     "rdm_net_forward_bf16": (C.c_int, [vp, vp, C.POINTER(vp), vp, sz, vp, sz, vp, vp]),
+    "rdm_net_encoder_output_bf16": (C.c_int, [vp, vp, sz, vp, i32, vp]),
+    "rdm_rel_num_tensors": (C.c_int, [i32]),
+    "rdm_rel_bf16_weight_bytes": (sz, [i32]),
+    "rdm_rel_bf16_prepare": (C.c_int, [i32, C.POINTER(vp), vp, sz, vp]),
+    "rdm_rel_bf16_workspace_bytes": (sz, [i32, i32]),
+    "rdm_rel_forward_bf16": (C.c_int, [i32, vp, i32, i32, vp, vp, sz, vp, vp]),
+    "rdm_rel_bf16_input_nchw": (C.c_int, [vp, i32, vp, i32, vp]),
+    "rdm_wsm_conv_bf16": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "rdm_wsm_deconv_bf16": (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
+    "rdm_wsm_strip_bf16": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "rdm_wsm_conv1x1_f32": (C.c_int, [vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]),
     "rdm_net_backward": (C.c_int, [vp, vp, C.POINTER(vp), C.POINTER(vp), vp, sz, i32, i32, vp]),
     "rdm_net_segment_range": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32)]),
     "rdm_net_num_backward_stages": (C.c_int, []),

@@ -50,6 +50,14 @@ int launch_f32_to_bf16_rows(const float* src, int ld_src, void* dst, int ld_dst,
 int launch_pack_w_bf16(const float* w_oihw, void* w_packed, int O, int I, int ld, int T, hipStream_t s);
 int launch_im2col_stem_bf16(const float* x, void* patches, int B, int H, int W, hipStream_t s);
 int launch_maxpool3s2_bf16(const void* X, void* Y, int ldy, int B, int H, int W, int C, hipStream_t s);
+// one dense block of the bf16 forward (net.hip): per layer BN-ReLU -> 1x1 (cin -> cbp, the 3x3's BN-ReLU in the epilogue) -> 3x3 (cbp -> 48)
+// written in place behind the block's channels.  rdm_net_forward_bf16 runs its four blocks through it, the relative decoders their own.
+struct DenseBf16Block {
+  unsigned short* blk; int B, H, W, M, ctot, cin0, layers, cbp; bool act3;
+  void* Y; float* partial; size_t partial_floats; unsigned* counters; int n_counters;
+  const void* w1[48]; const void* w3[48]; const float* bn1[48]; const float* bn2[48];
+};
+int dense_block_bf16(const DenseBf16Block& d, hipStream_t s);
 int launch_trans_pool_bf16(const void* X, int ldx, const float* sc, const float* sh, void* P, int B, int H, int W, int C, hipStream_t s);
 
 }  // namespace rdm

@@ -871,6 +871,43 @@ int backward_transition(NetImpl& n, int t, void* ws, void* const* T, void* const
 }
 
 }  // namespace
+
+/* one dense block of the bf16 forward: per layer BN-ReLU -> 1x1 (cin -> cb, the consumer's BN-ReLU in the epilogue: eval mode knows it
+ * ahead) -> 3x3 (cb -> 48) written in place behind the block's channels.  d_1's block in rdm_net_forward_bf16 and the relative
+ * decoders' blocks (wsm_bf16.hip) enqueue exactly these launches. */
+int dense_block_bf16(const DenseBf16Block& d, hipStream_t s) {
+  int rc;
+  RDM_CHECK_ARG(d.layers > 0 && d.layers <= 48, "dense block: 1..48 layers");
+  for (int i = 0; i < d.layers; ++i) {
+    const int cin = d.cin0 + i * GROWTH;
+    const float* bn1 = d.bn1[i];
+    const float* bn2 = d.bn2[i];
+    const int cbp = d.cbp;
+    GemmBf16Args a{};
+    a.X = d.blk; a.ldx = d.ctot; a.K = cin; a.scale = bn1; a.shift = bn1 + cin;
+    a.W = d.w1[i]; a.ldw = cin;
+    a.out = d.Y; a.ldc = cbp; a.M = d.M; a.N = cbp; a.oscale = bn2; a.oshift = bn2 + cbp;
+    a.partial = d.partial; a.partial_floats = d.partial_floats;
+    if ((rc = launch_gemm_bf16(a, false, s))) return rc;
+    if (d.act3) {
+      Conv3ActArgs c{};
+      c.Y = d.Y; c.ldy = cbp; c.C = cbp; c.Wimg = d.w3[i];
+      c.out = d.blk + cin; c.ldc = d.ctot; c.B = d.B; c.H = d.H; c.W = d.W;
+      c.partial = d.partial; c.partial_floats = d.partial_floats;
+      c.counters = d.counters; c.n_counters = d.n_counters;
+      if ((rc = launch_conv3x3_act_bf16(c, s))) return rc;
+    } else {
+      Conv3Bf16Args c{};
+      c.Y = d.Y; c.ldy = cbp; c.C = cbp;
+      c.Wt = d.w3[i]; c.wtap = (long)GROWTH * cbp; c.ldw = cbp;
+      c.out = d.blk + cin; c.ldc = d.ctot; c.B = d.B; c.H = d.H; c.W = d.W; c.M = d.M;
+      c.partial = d.partial; c.partial_floats = d.partial_floats;
+      if ((rc = launch_conv3x3_bf16(c, s))) return rc;
+    }
+  }
+  return RDM_OK;
+}
+
 }  // namespace rdm
 
 using namespace rdm;
@@ -1160,33 +1197,18 @@ int rdm_net_forward_bf16(rdm_net* net, const float* x, void* const* T, const voi
   for (int b = 0; b < 4; ++b) {
     const BlockGeom& g = n.bg[b];
     unsigned short* blk = at<unsigned short>(ws, n.bf_blk[b]);
-    for (int i = 0; i < kBlocks[b].layers; ++i) {
-      const NetImpl::Bf16Layer& W = n.bfl[b][i];
-      const int cin = kBlocks[b].cin + i * GROWTH;
-      const float* bn1 = at<float>(wb, W.bn1);
-      const float* bn2 = at<float>(wb, W.bn2);
-      const int cbp = n.bf_cbp[b];
-      GemmBf16Args a{};                                      // BN-ReLU -> 1x1 (cin -> cb) -> the 3x3's BN-ReLU in the epilogue (eval mode: known ahead)
-      a.X = blk; a.ldx = g.ctot; a.K = cin; a.scale = bn1; a.shift = bn1 + cin;
-      a.W = at<char>(wb, W.w1); a.ldw = cin;
-      a.out = at<char>(ws, n.bf_Y); a.ldc = cbp; a.M = g.M; a.N = cbp; a.oscale = bn2; a.oshift = bn2 + cbp;
-      a.partial = at<float>(ws, n.bf_partial); a.partial_floats = n.bf_partial_floats;
-      if ((rc = launch_gemm_bf16(a, false, s))) return rc;
-      if (n.bf_act3[b]) {                                    // 3x3 (cb -> 48) on the activated tensor, written in place behind the block's channels
-        Conv3ActArgs c{};
-        c.Y = at<char>(ws, n.bf_Y); c.ldy = cbp; c.C = cbp; c.Wimg = at<char>(wb, W.w3);
-        c.out = blk + cin; c.ldc = g.ctot; c.B = n.B; c.H = g.H; c.W = g.W;
-        c.partial = at<float>(ws, n.bf_partial); c.partial_floats = n.bf_partial_floats;
-        c.counters = at<unsigned>(ws, n.bf_counters); c.n_counters = NetImpl::kBfCounters;
-        if ((rc = launch_conv3x3_act_bf16(c, s))) return rc;
-      } else {
-        Conv3Bf16Args c{};
-        c.Y = at<char>(ws, n.bf_Y); c.ldy = cbp; c.C = cbp;
-        c.Wt = at<char>(wb, W.w3); c.wtap = (long)GROWTH * cbp; c.ldw = cbp;
-        c.out = blk + cin; c.ldc = g.ctot; c.B = n.B; c.H = g.H; c.W = g.W; c.M = g.M;
-        c.partial = at<float>(ws, n.bf_partial); c.partial_floats = n.bf_partial_floats;
-        if ((rc = launch_conv3x3_bf16(c, s))) return rc;
+    {
+      DenseBf16Block d{};
+      d.blk = blk; d.B = n.B; d.H = g.H; d.W = g.W; d.M = g.M; d.ctot = g.ctot; d.cin0 = kBlocks[b].cin; d.layers = kBlocks[b].layers;
+      d.cbp = n.bf_cbp[b]; d.act3 = n.bf_act3[b];
+      d.Y = at<char>(ws, n.bf_Y); d.partial = at<float>(ws, n.bf_partial); d.partial_floats = n.bf_partial_floats;
+      d.counters = at<unsigned>(ws, n.bf_counters); d.n_counters = NetImpl::kBfCounters;
+      for (int i = 0; i < kBlocks[b].layers; ++i) {
+        const NetImpl::Bf16Layer& W = n.bfl[b][i];
+        d.w1[i] = at<char>(wb, W.w1); d.w3[i] = at<char>(wb, W.w3);
+        d.bn1[i] = at<float>(wb, W.bn1); d.bn2[i] = at<float>(wb, W.bn2);
       }
+      if ((rc = dense_block_bf16(d, s))) return rc;
     }
     if (b < 3) {
       const BlockGeom& gn = n.bg[b + 1];
@@ -1209,6 +1231,20 @@ int rdm_net_forward_bf16(rdm_net* net, const float* x, void* const* T, const voi
     if ((rc = launch_gemm_bf16(a, true, s))) return rc;
     if ((rc = launch_nhwc_to_nchw(at<float>(ws, n.bf_logits), 192, logits_nchw, n.B, 180, g.H * g.W, s))) return rc;
   }
+  return RDM_OK;
+}
+
+/* the encoder's output (trans_e4, RDM_Net.py:94) of the last rdm_net_forward_bf16 on this workspace: the first 1056 channels of the
+ * decoder block's NHWC bf16 buffer, copied to `out` (B*h*w rows of row stride `ldo` >= 1056 bf16 elements) - e.g. straight into the
+ * block buffer of a relative decoder (rdm_rel_forward_bf16).  The bf16 twin of rdm_net_encoder_output. */
+int rdm_net_encoder_output_bf16(const rdm_net* net, const void* ws, size_t ws_bytes, void* out, int32_t ldo, rdm_stream_t stream) {
+  RDM_CHECK_ARG(net && ws && out, "NULL argument");
+  const NetImpl& n = *reinterpret_cast<const NetImpl*>(net);
+  RDM_CHECK_ARG(ldo >= kBlocks[3].cin, "ldo must be >= %d", kBlocks[3].cin);
+  if (ws_bytes < n.bf_total) { set_error("workspace too small: %zu < %zu", ws_bytes, n.bf_total); return RDM_ERR_WORKSPACE_TOO_SMALL; }
+  const BlockGeom& g = n.bg[3];
+  RDM_HIP_OK(hipMemcpy2DAsync(out, (size_t)ldo * 2, static_cast<const char*>(ws) + n.bf_blk[3], (size_t)g.ctot * 2, (size_t)kBlocks[3].cin * 2, g.M,
+                              hipMemcpyDeviceToDevice, stream));
   return RDM_OK;
 }
 

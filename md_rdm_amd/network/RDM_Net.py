@@ -222,6 +222,57 @@ class Decoder(nn.Module):
         self.conv2 = nn.Conv2d(in_channels=_wsm_output_planes(id), out_channels=180, kernel_size=1)
         self.ord_layer = Ordinal_Layer(id, DORN, quant)
 
+    # ---- bf16 inference (rdm_rel_forward_bf16, csrc/wsm_bf16.hip): prepared weights are derived data, rebuilt when stale ----
+    def set_precision(self, precision):
+        """"f32" (default) or "bf16": ``features`` of an eval-mode relative decoder on the bf16 path (training still runs in f32 only)."""
+        if precision not in ("f32", "bf16"):
+            raise ValueError("precision must be 'f32' or 'bf16'")
+        self.precision = precision
+        return self
+
+    def mark_weights_changed(self):
+        self._bf16_rel_stale = True
+
+    def load_state_dict(self, *a, **k):
+        self._bf16_rel_stale = True
+        return super().load_state_dict(*a, **k)
+
+    def _apply(self, fn, *a, **k):
+        self._bf16_rel_stale = True
+        return super()._apply(fn, *a, **k)
+
+    def _prepare_bf16(self, device):
+        L = _lib.lib()
+        tensors = list(self.state_dict().values())
+        if len(tensors) != L.rdm_rel_num_tensors(self.id):
+            raise _lib.RdmError("decoder %d: %d state tensors, the library expects %d" % (self.id, len(tensors), L.rdm_rel_num_tensors(self.id)))
+        nbytes = int(L.rdm_rel_bf16_weight_bytes(self.id))
+        w = self.__dict__.get("_bf16_rel_w")
+        if w is None or w.numel() < nbytes or w.device != device:
+            w = self.__dict__["_bf16_rel_w"] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            self._bf16_rel_stale = True
+        if self.__dict__.get("_bf16_rel_stale", True):
+            table = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+            _lib.check(L.rdm_rel_bf16_prepare(self.id, table, C.c_void_p(w.data_ptr()), nbytes, _lib.stream()))
+            self._bf16_rel_stale = False
+        return w
+
+    def features_bf16(self, enc, ld_enc, batch):
+        """The bf16 forward from the encoder output as (batch*8*8, ld_enc) NHWC bf16 (any dtype holding those bytes): (B,1,S,S) f32."""
+        L = _lib.lib()
+        if self.training:
+            raise _lib.RdmError("the bf16 path is inference only (eval-mode BatchNorm): call eval(), or use the f32 path to train")
+        w = self._prepare_bf16(enc.device)
+        ws_bytes = int(L.rdm_rel_bf16_workspace_bytes(self.id, batch))
+        ws = self.__dict__.get("_bf16_rel_ws")
+        if ws is None or ws.numel() < ws_bytes or ws.device != enc.device:
+            ws = self.__dict__["_bf16_rel_ws"] = torch.empty(ws_bytes, dtype=torch.uint8, device=enc.device)
+        S = 2 ** (self.id - 3)
+        out = torch.empty(batch, 1, S, S, dtype=torch.float32, device=enc.device)
+        _lib.check(L.rdm_rel_forward_bf16(self.id, _lib.ptr(enc), ld_enc, batch, C.c_void_p(w.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes, _lib.ptr(out),
+                                          _lib.stream()))
+        return out
+
     def features(self, x):
         """dense block -> WSM chain -> conv1 (:151-157): the one-channel map the relative head consumes, (B,1,S,S)."""
         from . import wsm
@@ -229,6 +280,17 @@ class Decoder(nn.Module):
             raise _lib.RdmError("Decoder runs on the GPU only")
         if self.id <= 5:
             raise _lib.RdmError("decoder %d is part of the native plan (DepthEstimationNet.forward); only the relative decoders 6..10 run standalone" % self.id)
+        if getattr(self, "precision", "f32") == "bf16":
+            if self.training:
+                raise _lib.RdmError("the bf16 path is inference only (eval-mode BatchNorm): call eval(), or set_precision('f32') to train")
+            B = x.shape[0]
+            if tuple(x.shape[1:]) != (1056, 8, 8):
+                raise _lib.RdmError("the bf16 relative decoders take the (B,1056,8,8) encoder output, got %s" % (tuple(x.shape),))
+            enc = torch.empty(B * 64, 1056, dtype=torch.bfloat16, device=x.device)
+            _lib.check(_lib.lib().rdm_rel_bf16_input_nchw(_lib.ptr(x.contiguous().float()), B, _lib.ptr(enc), 1056, _lib.stream()))
+            return self.features_bf16(enc, 1056, B)
+        if self.training:
+            self._bf16_rel_stale = True                 # the training forward updates the running statistics in place (a kernel: no _version bump)
         with torch.no_grad():
             h = _dense_block_forward(self.dense_layer, x.float(), self.training)
             if len(self.wsm_block):
@@ -498,7 +560,9 @@ class DepthEstimationNet(BaseModel):
     def set_precision(self, precision):
         """"f32" (default: exact-f32 MFMA, training and inference) or "bf16" (inference only: ``model.eval()`` forward runs with bf16
         weights / activations, f32 accumulation and f32 BatchNorm affines; the DORN tail stays f64).  bf16 does not meet the 1e-4
-        parity bar of the f32 path; its tolerance is stated in tests/test_gpu_bf16.py."""
+        parity bar of the f32 path; its tolerance is stated in tests/test_gpu_bf16.py.  The relative decoders (``relative_decoders``) run on the
+        bf16 path too (rdm_rel_forward_bf16: dense block, WSM chain and conv1 in bf16; the heads unchanged), tolerance in
+        tests/test_gpu_relative_bf16.py."""
         if precision not in ("f32", "bf16"):
             raise ValueError("precision must be 'f32' or 'bf16'")
         self.precision = precision
@@ -530,6 +594,8 @@ class DepthEstimationNet(BaseModel):
         table = (C.c_void_p * len(tensors))(*[t.data_ptr() if t.numel() else None for t in tensors])
         if self._bf16_stale:
             _lib.check(L.rdm_net_bf16_prepare(h, table, C.c_void_p(self._bf16_w.data_ptr()), nbytes, _lib.stream()))
+            for did in self.relative_ids:                   # the relative decoders' prepared weights follow the same staleness rule
+                getattr(self, "d_%d" % did).mark_weights_changed()
             self._bf16_stale = False
         return h, table, nbytes
 
@@ -551,7 +617,16 @@ class DepthEstimationNet(BaseModel):
         logits = torch.empty(B, 180, oh, ow, dtype=torch.float32, device=x.device)
         _lib.check(L.rdm_net_forward_bf16(h, _lib.ptr(x), table, C.c_void_p(self._bf16_w.data_ptr()), wbytes, C.c_void_p(self._bf16_ws.data_ptr()),
                                           ws_bytes, _lib.ptr(logits), _lib.stream()))
+        self._last_bf16 = (h, ws_bytes, B)
         return logits
+
+    def encoder_output_bf16(self):
+        """(B*h*w, 1056) bf16 NHWC: the encoder output (trans_e4, RDM_Net.py:94) of the last bf16 forward - the relative decoders' input."""
+        h, ws_bytes, B = self._last_bf16
+        _, _, oh, ow = next(v for k, v in self._plans.items() if v[0] is h)
+        out = torch.empty(B * oh * ow, 1056, dtype=torch.bfloat16, device=self._bf16_ws.device)
+        _lib.check(_lib.lib().rdm_net_encoder_output_bf16(h, C.c_void_p(self._bf16_ws.data_ptr()), ws_bytes, _lib.ptr(out), 1056, _lib.stream()))
+        return out
 
     def encoder_output(self):
         """(B,1056,h,w) float32: the encoder output (trans_e4, RDM_Net.py:94) of the last f32 forward - what every decoder consumes."""
@@ -587,9 +662,8 @@ class DepthEstimationNet(BaseModel):
 
     # ---- the reference forward (RDM_Net.py:70-135) -----------------------------------------
     def forward(self, x):
-        if self.precision == "bf16":
-            if self.relative_ids:
-                raise _lib.RdmError("the relative decoders run on the f32 path only")
+        bf16 = self.precision == "bf16"
+        if bf16:
             logits = self._native_forward_bf16(x)                               # inference only; no autograd node
         else:
             params = [p for _, p in self.stack_parameters()] if self._flat is None else [p for _, p, _, _, _ in self._flat[2]]
@@ -609,9 +683,16 @@ class DepthEstimationNet(BaseModel):
             if (H, W) != (8, 8):
                 raise _lib.RdmError("the relative decoders need the square 8x8 encoder output (226/228-pixel inputs), got %dx%d" % (H, W))
             with torch.no_grad():
-                enc = self.encoder_output()                                      # trans_e4 output (B,1056,8,8) of the forward above
+                if bf16:                                                         # trans_e4 output as (B*64, 1056) bf16 NHWC, no layout pass
+                    enc = self.encoder_output_bf16()
+                else:
+                    enc = self.encoder_output()                                  # trans_e4 output (B,1056,8,8) of the forward above
                 for did in self.relative_ids:
-                    x_dk = getattr(self, "d_%d" % did)(enc)                      # (B,1,S,S) relative map, S = 2^(did-3)
+                    dec = getattr(self, "d_%d" % did)
+                    if bf16:
+                        x_dk = dec.ord_layer(dec.features_bf16(enc, 1056, B))    # (B,1,S,S) relative map, S = 2^(did-3)
+                    else:
+                        x_dk = dec(enc)
                     rows.append(cp.decompose_depth_map([], x_dk, did - 3, relative_map=True)[::-1])
         y_hat = cp.relative_fine_detail_matrix(rows, use_cuda)                  # :126
         y_hat = self.weight_layer(y_hat)                                        # :133

@@ -71,7 +71,7 @@ def main(argv=None):
     parser.add_argument("--size", type=int, nargs=2, default=[226, 226], help="input HxW (module.py:19 feeds 226x226)")
     parser.add_argument("--checkpoint_dir", type=str, default=None, help="keep the best checkpoint by val_delta1 here (train.py:41-47: ModelCheckpoint(save_top_k=1, monitor='val_delta1', mode='max'))")
     parser.add_argument("--resume", type=str, default=None, help="Lightning .ckpt or state_dict to start from")
-    parser.add_argument("--relative_decoders", type=int, nargs="*", default=[], help="subset of 6 7 8 9: the relative decoders the reference keeps commented out (RDM_Net.py:57-60)")
+    parser.add_argument("--relative_decoders", type=int, nargs="*", default=[], help="subset of 6 7 8 9 10: the relative decoders the reference keeps commented out (RDM_Net.py:57-61)")
     args = parser.parse_args(argv)
     if args.precision not in (16, 32):
         raise SystemExit("--precision must be 16 or 32")
