@@ -232,6 +232,17 @@ int rdm_gemm_bf16_act(const void* x, int32_t ldx, int32_t k, const float* scale,
 size_t rdm_conv3x3_bf16_workspace_bytes(int32_t channels, int32_t batch, int32_t h, int32_t w);
 int rdm_conv3x3_bf16(const void* y, int32_t ldy, int32_t channels, const float* scale, const float* shift, const void* w_packed, void* out,
                      int32_t ldc, int32_t batch, int32_t h, int32_t w, void* workspace, size_t workspace_bytes, rdm_stream_t stream);
+/* Their training forms (the statistics epilogues of rdm_rel_forward_bf16_train): the RAW output is stored as bf16 (no output activation),
+ * and sum[n] / sumsq[n] (f64) receive the per-channel sum and sum of squares of the STORED, bf16-rounded values.  f32 per tile of >= 8
+ * pixels, tiles added in f64 in a fixed order after the K-split partial sums are reduced; no atomics (same bits every run).  workspace: 256-byte
+ * aligned, at least rdm_bf16_stats_workspace_bytes(m, n) (n = 48 for the 3x3) of statistics scratch; what lies beyond it holds the K-split's
+ * f32 partial sums (none: no split). */
+size_t rdm_bf16_stats_workspace_bytes(int32_t m, int32_t n);
+int rdm_gemm_bf16_stats(const void* x, int32_t ldx, int32_t k, const float* scale, const float* shift, const void* w, int32_t ldw, void* out, int32_t ldc,
+                        int32_t m, int32_t n, double* sum, double* sumsq, void* workspace, size_t workspace_bytes, rdm_stream_t stream);
+int rdm_conv3x3_bf16_stats(const void* y, int32_t ldy, int32_t channels, const float* scale, const float* shift, const void* w_packed, void* out,
+                           int32_t ldc, int32_t batch, int32_t h, int32_t w, double* sum, double* sumsq, void* workspace, size_t workspace_bytes,
+                           rdm_stream_t stream);
 /* The same 3x3 on an ALREADY ACTIVATED input (the form rdm_net_forward_bf16 runs: in eval mode the producing 1x1 applies BatchNorm +
  * ReLU in its epilogue - rdm_gemm_bf16_act - so the 3x3 has no prologue and both operands reach LDS by DMA, zero padding included):
  *   rdm_conv3x3_act_bf16_pack  w (48, channels, 3, 3) f32 OIHW -> the fragment-order bf16 image the kernel streams
@@ -421,6 +432,21 @@ size_t rdm_rel_bf16_workspace_bytes(int32_t id, int32_t batch);
 int rdm_rel_forward_bf16(int32_t id, const void* enc, int32_t ld_enc, int32_t batch, const void* wbuf, void* workspace, size_t workspace_bytes,
                          float* out_map, rdm_stream_t stream);
 int rdm_rel_bf16_input_nchw(const float* x_nchw, int32_t batch, void* enc, int32_t ld_enc, rdm_stream_t stream);
+/* The same decoders' TRAINING-mode forward on the bf16 path (the reference's `--precision 16`, AMP O2: narrow conv operands, float32
+ * BatchNorm).  The dense block's BatchNorms use the batch statistics and update the running statistics like nn.BatchNorm2d (momentum 0.1,
+ * unbiased variance, num_batches_tracked + 1); forward only (the reference's Lloyd step severs the graph above these decoders).
+ *   rdm_rel_bf16_train_workspace_bytes  activation workspace of one training forward at `batch` (256-byte aligned, caller-owned)
+ *   rdm_rel_forward_bf16_train          enc as rdm_rel_forward_bf16 (16-byte aligned, ld_enc a multiple of 8); enc_stats = [sum 1056 | sumsq 1056]
+ *                                       f64 column statistics of enc (rdm_colstats_bf16: computed once, shared by the decoders of one forward;
+ *                                       NULL = computed here); `tensors` = the decoder's LIVE state_dict tensors in order - the norm1 / norm2
+ *                                       running_mean, running_var and num_batches_tracked are updated in place; wbuf = the conv weights packed by
+ *                                       rdm_rel_bf16_prepare (its folded eval-mode affines are not read, and are stale afterwards).
+ *                                       Deterministic: no atomics, the same bits every run.
+ *   rdm_colstats_bf16                   sum[c] / sumsq[c] (f64) of x (m, ldx) bf16 over its first c columns (c, ldx multiples of 8, x 16-byte aligned) */
+size_t rdm_rel_bf16_train_workspace_bytes(int32_t id, int32_t batch);
+int rdm_rel_forward_bf16_train(int32_t id, const void* enc, int32_t ld_enc, const double* enc_stats, int32_t batch, void* const* tensors, const void* wbuf,
+                               void* workspace, size_t workspace_bytes, float* out_map, rdm_stream_t stream);
+int rdm_colstats_bf16(const void* x, int32_t ldx, int32_t m, int32_t c, double* sum, double* sumsq, rdm_stream_t stream);
 /* The WSM conv kernel's epilogue modes as operators (RDM_Net.py:163-236; the decoder forward above enqueues the same launches).  x: NHWC
  * bf16 (B,h,w, ldx), channels [xoff, xoff + cin); w: bf16 [rows][K] with K = taps * pad32(cin), k = tap * pad32(cin) + ci (zero padded),
  * rows allocated up to a multiple of 64; bias f32 (optional).  16-byte aligned operands; ldx, xoff multiples of 8.

@@ -97,6 +97,12 @@ _SIGNATURES = {
     "rdm_rel_bf16_workspace_bytes": (sz, [i32, i32]),
     "rdm_rel_forward_bf16": (C.c_int, [i32, vp, i32, i32, vp, vp, sz, vp, vp]),
     "rdm_rel_bf16_input_nchw": (C.c_int, [vp, i32, vp, i32, vp]),
+    "rdm_rel_bf16_train_workspace_bytes": (sz, [i32, i32]),
+    "rdm_rel_forward_bf16_train": (C.c_int, [i32, vp, i32, vp, i32, C.POINTER(vp), vp, vp, sz, vp, vp]),
+    "rdm_colstats_bf16": (C.c_int, [vp, i32, i32, i32, vp, vp, vp]),
+    "rdm_bf16_stats_workspace_bytes": (sz, [i32, i32]),
+    "rdm_gemm_bf16_stats": (C.c_int, [vp, i32, i32, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "rdm_conv3x3_bf16_stats": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "rdm_wsm_conv_bf16": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "rdm_wsm_deconv_bf16": (C.c_int, [vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "rdm_wsm_strip_bf16": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),

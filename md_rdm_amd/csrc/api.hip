@@ -439,6 +439,42 @@ int rdm_gemm_bf16_act(const void* x, int32_t ldx, int32_t k, const float* scale,
   return launch_gemm_bf16(a, false, stream);
 }
 
+// the statistics epilogues' operator entries: the f32 statistics scratch at the front of the workspace, the K-split partial sums behind it
+static size_t stats_scratch_bytes(long m, int n) { return (bf16_stats_floats(m, n) * sizeof(float) + 255) & ~(size_t)255; }
+
+size_t rdm_bf16_stats_workspace_bytes(int32_t m, int32_t n) { return m > 0 && n > 0 ? stats_scratch_bytes(m, n) : 0; }
+
+int rdm_gemm_bf16_stats(const void* x, int32_t ldx, int32_t k, const float* scale, const float* shift, const void* w, int32_t ldw, void* out, int32_t ldc,
+                        int32_t m, int32_t n, double* sum, double* sumsq, void* workspace, size_t workspace_bytes, rdm_stream_t stream) {
+  RDM_CHECK_ARG(x && w && out && sum && sumsq && workspace && m > 0 && n > 0 && k > 0 && ldx >= k && ldw >= k && ldc >= n, "gemm_bf16_stats: bad argument");
+  RDM_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && workspace_bytes >= stats_scratch_bytes(m, n), "gemm_bf16_stats: workspace must be 256-byte aligned and >= rdm_bf16_stats_workspace_bytes(m, n)");
+  const size_t sb = stats_scratch_bytes(m, n);
+  GemmBf16Args a{};
+  a.X = x; a.ldx = ldx; a.K = k; a.scale = scale; a.shift = shift; a.W = w; a.ldw = ldw; a.out = out; a.ldc = ldc; a.M = m; a.N = n;
+  a.osum = sum; a.osq = sumsq; a.stats = static_cast<float*>(workspace); a.stats_floats = sb / sizeof(float);
+  a.partial = workspace_bytes > sb ? reinterpret_cast<float*>(static_cast<char*>(workspace) + sb) : nullptr;
+  a.partial_floats = (workspace_bytes - sb) / sizeof(float);
+  return launch_gemm_bf16(a, false, stream);
+}
+
+int rdm_conv3x3_bf16_stats(const void* y, int32_t ldy, int32_t channels, const float* scale, const float* shift, const void* w_packed, void* out,
+                           int32_t ldc, int32_t batch, int32_t h, int32_t w, double* sum, double* sumsq, void* workspace, size_t workspace_bytes,
+                           rdm_stream_t stream) {
+  RDM_CHECK_ARG(y && w_packed && out && sum && sumsq && workspace && (scale == nullptr) == (shift == nullptr) && batch > 0 && h > 0 && w > 0 && channels > 0 &&
+                ldy >= channels && ldc >= 48, "conv3x3_bf16_stats: bad argument");
+  RDM_CHECK_ARG((long)batch * h * w < (1L << 30), "conv3x3_bf16_stats: too many pixels for 32-bit indices");
+  const long M = (long)batch * h * w;
+  const size_t sb = stats_scratch_bytes(M, 48);
+  RDM_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && workspace_bytes >= sb, "conv3x3_bf16_stats: workspace must be 256-byte aligned and >= rdm_bf16_stats_workspace_bytes(B*H*W, 48)");
+  Conv3Bf16Args a{};
+  a.Y = y; a.ldy = ldy; a.C = channels; a.scale = scale; a.shift = shift; a.Wt = w_packed; a.wtap = 48L * channels; a.ldw = channels;
+  a.out = static_cast<unsigned short*>(out); a.ldc = ldc; a.B = batch; a.H = h; a.W = w; a.M = (int)M;
+  a.osum = sum; a.osq = sumsq; a.stats = static_cast<float*>(workspace); a.stats_floats = sb / sizeof(float);
+  a.partial = workspace_bytes > sb ? reinterpret_cast<float*>(static_cast<char*>(workspace) + sb) : nullptr;
+  a.partial_floats = (workspace_bytes - sb) / sizeof(float);
+  return launch_conv3x3_bf16(a, stream);
+}
+
 size_t rdm_conv3x3_bf16_workspace_bytes(int32_t channels, int32_t batch, int32_t h, int32_t w) {
   if (channels <= 0 || batch <= 0 || h <= 0 || w <= 0) return 0;
   const long M = (long)batch * h * w;

@@ -13,6 +13,10 @@ struct GemmBf16Args {        // out[m][n] = bias[n] + sum_k f(X[m][k]) * W[n][k]
   float* partial; size_t partial_floats;   // optional f32 scratch for a K-split ([split][M][N] partial sums + one tiny reduction launch)
   unsigned x_bytes, w_bytes, p_bytes, o_bytes;   // set by the launcher (buffer descriptors)
   int abl;                                 // development builds: ablation bits (0 in the shipped build)
+  // training-mode statistics epilogue (osum != NULL; gemm_bf16_kernel<..., STATS = true>, no panel kernel, no oscale): per-channel sum and sum of
+  // squares of the STORED (bf16-rounded) outputs - f32 per wave row tile into `stats` ([tile][sum N | sq N]), combined in f64 in tile order
+  double* osum; double* osq;
+  float* stats; size_t stats_floats;       // >= bf16_stats_floats(M, N)
 };
 
 struct Conv3Bf16Args {       // out[m][n] = sum_{tap,c} relu(Y[pix(m,tap)][c]*scale[c]+shift[c]) * Wt[tap][n][c], zero padding, n < 48
@@ -25,6 +29,9 @@ struct Conv3Bf16Args {       // out[m][n] = sum_{tap,c} relu(Y[pix(m,tap)][c]*sc
   int split;                               // set by the launcher
   int slots;                               // set by the launcher: zero-padded LDS image slots (pixels) the kernel may use, multiple of 8
   unsigned y_bytes, w_bytes, p_bytes;
+  // training-mode statistics epilogue (osum != NULL; conv3x3_bf16_kernel<..., STATS = true>): as GemmBf16Args, over the 48 outputs
+  double* osum; double* osq;
+  float* stats; size_t stats_floats;       // >= bf16_stats_floats(M, 48)
 };
 
 struct Conv3ActArgs {        // out[m][n] = sum_{tap,c} Y[pix(m,tap)][c] * w[n][c][tap] on an ALREADY ACTIVATED input, zero padding, n < 48
@@ -40,6 +47,10 @@ struct Conv3ActArgs {        // out[m][n] = sum_{tap,c} Y[pix(m,tap)][c] * w[n][
 };
 
 int launch_gemm_bf16(const GemmBf16Args& a, bool out_f32, hipStream_t s);
+// f32 scratch the statistics epilogues need for M rows x N channels (tiles of >= 8 rows, two values per channel and tile)
+inline size_t bf16_stats_floats(long M, int N) { return (size_t)2 * N * ((M + 7) / 8 + 4); }
+// per-channel f64 sum / sum of squares of x[0, M) x [0, C) bf16 (row stride ldx; C, ldx multiples of 8): f32 per thread, f64 in a fixed order
+int launch_colstats_bf16(const void* x, int ldx, int M, int C, double* sum, double* sq, hipStream_t s);
 int launch_conv3x3_act_bf16(const Conv3ActArgs& a, hipStream_t s);      // RDM_ERR_UNSUPPORTED when the geometry does not fit the LDS (nothing launched)
 size_t conv3x3_act_partial_floats(int C, int B, int H, int W);          // scratch the heuristic would like
 int conv3x3_act_tiles(int B, int H, int W);                             // upper bound of the tile count (counters needed)
@@ -58,6 +69,19 @@ struct DenseBf16Block {
   const void* w1[48]; const void* w3[48]; const float* bn1[48]; const float* bn2[48];
 };
 int dense_block_bf16(const DenseBf16Block& d, hipStream_t s);
+// the same block in TRAINING mode (net.hip): BatchNorm from batch statistics, running statistics updated like nn.BatchNorm2d.  Per layer:
+// finalize norm1 over [0, cin) -> 1x1 with the norm1 BN-ReLU prologue, raw Y + its statistics -> finalize norm2 -> 3x3 with the norm2 BN-ReLU
+// prologue into the block + the statistics of its 48 channels (norm1 of every later layer).  bsum / bsq [ctot] f64 hold the statistics of
+// channels [0, cin0) on entry; gamma / beta / running buffers are the live tensors (nbt: int64 num_batches_tracked).
+struct DenseBf16TrainBlock {
+  unsigned short* blk; int B, H, W, M, ctot, cin0, layers, cb;
+  void* Y; float* partial; size_t partial_floats; float* stats; size_t stats_floats;
+  double* bsum; double* bsq; double* ysum; double* ysq; float* aff1; float* aff2;     // aff1 [4][ctot] / aff2 [4][cb] f32: scale | shift | mean | rstd
+  const void* w1[48]; const void* w3[48];
+  const float* g1[48]; const float* b1[48]; float* rm1[48]; float* rv1[48]; long long* nbt1[48];
+  const float* g2[48]; const float* b2[48]; float* rm2[48]; float* rv2[48]; long long* nbt2[48];
+};
+int dense_block_bf16_train(const DenseBf16TrainBlock& d, hipStream_t s);
 int launch_trans_pool_bf16(const void* X, int ldx, const float* sc, const float* sh, void* P, int B, int H, int W, int C, hipStream_t s);
 
 }  // namespace rdm

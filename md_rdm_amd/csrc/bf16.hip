@@ -74,7 +74,24 @@ __device__ __forceinline__ void xcd_order(int& bx, int& by) {      // see igemm.
 // Block = 4 wave64s (WM x WN), wave tile (MT*16 pixels) x (NT*16 channels), K walked in 64-deep steps (2 MFMA k-steps).
 // global -> registers (next step's loads in flight under this step's MFMAs) -> BN-ReLU -> swizzled LDS, 2 buffers, 1 barrier / step.
 // ---------------------------------------------------------------------------------------------
-template <int MT, int NT, int WM, int WN, int BK, int NS, bool OUT_F32>
+// sum and sum of squares of v over the 16 pixels (lanes l16) of a 16-lane group: fixed butterfly order
+__device__ __forceinline__ void group16_sums(float4& s, float4& q) {
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) {
+    s.x += __shfl_xor(s.x, o); s.y += __shfl_xor(s.y, o); s.z += __shfl_xor(s.z, o); s.w += __shfl_xor(s.w, o);
+    q.x += __shfl_xor(q.x, o); q.y += __shfl_xor(q.y, o); q.z += __shfl_xor(q.z, o); q.w += __shfl_xor(q.w, o);
+  }
+}
+// accumulate the bf16-rounded values of one stored 8-byte group (4 channels) into the lane's statistics
+__device__ __forceinline__ void acc_stats(uint2 pk, bool valid, float4& s, float4& q) {
+  const float r0 = valid ? bf_lo(pk.x) : 0.f, r1 = valid ? bf_hi(pk.x) : 0.f, r2 = valid ? bf_lo(pk.y) : 0.f, r3 = valid ? bf_hi(pk.y) : 0.f;
+  s.x += r0; s.y += r1; s.z += r2; s.w += r3;
+  q.x = fmaf(r0, r0, q.x); q.y = fmaf(r1, r1, q.y); q.z = fmaf(r2, r2, q.z); q.w = fmaf(r3, r3, q.w);
+}
+
+// STATS (training form): the raw output is stored as bf16 and the wave's MT*16 pixels give one f32 row of statistics per channel (the
+// stored values: bf16-rounded); the launcher combines the rows in f64.  The eval instantiations (STATS = false) compile as before.
+template <int MT, int NT, int WM, int WN, int BK, int NS, bool OUT_F32, bool STATS = false>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBf16Args p) {
   constexpr int BM = MT * 16 * WM, BN = NT * 16 * WN;
   constexpr int CH = BK / 8, RP = 256 / CH;                          // 16-byte chunks per row; rows covered by one pass of the 256 threads
@@ -206,6 +223,30 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBf16Args p) {
     return;
   }
 
+  if constexpr (STATS) {                                              // raw bf16 output + statistics of the stored values
+    const int trow = (m0 + wrow) / (MT * 16);                         // this wave's row of the statistics scratch
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int n = n0 + wcol + j * 16 + g * 4;
+      float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f), ss = b4, qq = b4;
+      if (p.bias && n < p.N) b4 = *reinterpret_cast<const float4*>(p.bias + n);
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const int m = m0 + wrow + i * 16 + l16;
+        const uint2 pk = make_uint2(pack2(acc[i][j][0] + b4.x, acc[i][j][1] + b4.y), pack2(acc[i][j][2] + b4.z, acc[i][j][3] + b4.w));
+        const bool ok = m < p.M && n < p.N;
+        if (ok) *reinterpret_cast<uint2*>(static_cast<unsigned short*>(p.out) + (long)m * p.ldc + n) = pk;
+        acc_stats(pk, ok, ss, qq);
+      }
+      group16_sums(ss, qq);                                            // all lanes take part (the 16-lane group shares n)
+      if (l16 == 0 && n < p.N) {
+        float* st = p.stats + (size_t)trow * 2 * p.N;
+        *reinterpret_cast<float4*>(st + n) = ss;
+        *reinterpret_cast<float4*>(st + p.N + n) = qq;
+      }
+    }
+    return;
+  }
   // D[row = channel 4g+r of the n-tile][col = pixel l16 of the m-tile]
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
@@ -445,7 +486,7 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
 // 9 x 3 x MT MFMAs of this one (register prefetch), 2 barriers per slab.
 // Dynamic LDS: [padded rows x (W+2)][32] bf16 + [9*48][32] bf16.
 // ---------------------------------------------------------------------------------------------
-template <int MT, int HL>      // HL >= ceil(image slots * 4 / 256): 16-byte chunks per thread and slab
+template <int MT, int HL, bool STATS = false>      // HL >= ceil(image slots * 4 / 256): 16-byte chunks per thread and slab; STATS: as gemm_bf16_kernel
 __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(Conv3Bf16Args p) {
   constexpr int BM = MT * 64, NT = 3, CS = 32, WLN = 7;              // 9*48*4 = 1728 weight chunks / 256 threads = 6.75
   extern __shared__ __attribute__((aligned(16))) unsigned short dyn[];
@@ -580,6 +621,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(Conv3Bf16Args p) {
         const int m = m0 + wrow + i * 16 + l16;
         if (m < p.M) *reinterpret_cast<float4*>(slab + (size_t)m * 48 + n) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
       }
+    }
+    return;
+  }
+  if constexpr (STATS) {                                              // one f32 statistics row per wave (its MT*16 pixels)
+    float* st = p.stats + (size_t)(blockIdx.x * 4 + wave) * 96;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int n = j * 16 + g * 4;
+      float4 ss = make_float4(0.f, 0.f, 0.f, 0.f), qq = ss;
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const int m = m0 + wrow + i * 16 + l16;
+        const uint2 pk = make_uint2(pack2(acc[i][j][0], acc[i][j][1]), pack2(acc[i][j][2], acc[i][j][3]));
+        if (m < p.M) *reinterpret_cast<uint2*>(p.out + (long)m * p.ldc + n) = pk;
+        acc_stats(pk, m < p.M, ss, qq);
+      }
+      group16_sums(ss, qq);
+      if (l16 == 0) { *reinterpret_cast<float4*>(st + n) = ss; *reinterpret_cast<float4*>(st + 48 + n) = qq; }
     }
     return;
   }
@@ -879,6 +938,80 @@ __global__ __launch_bounds__(256) void k_reduce_partials_bf16(const float* __res
   }
 }
 
+// the same reduction in the training form: out = bf16(sum_s partial[s]) (no activation), and per 8-row chunk the f32 sum / sum of squares
+// of the stored values of 4 channels -> stats[chunk][sum N | sq N]  (short chunks: many threads, few dependent loads each)
+constexpr int RED_ROWS = 8;
+__global__ __launch_bounds__(256) void k_reduce_partials_stats_bf16(const float* __restrict__ partial, int split, int M, int N, unsigned short* __restrict__ out,
+                                                                    int ldc, float* __restrict__ stats) {
+  const int n4 = N / 4, idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (M + RED_ROWS - 1) / RED_ROWS * n4) return;
+  const int c = idx / n4, n = (idx - c * n4) * 4;
+  float4 ss = make_float4(0.f, 0.f, 0.f, 0.f), qq = ss;
+#pragma unroll
+  for (int r = 0; r < RED_ROWS; ++r) {
+    const int m = c * RED_ROWS + r;
+    if (m >= M) break;
+    float4 a = *reinterpret_cast<const float4*>(partial + (size_t)m * N + n);
+    for (int s = 1; s < split; ++s) {
+      const float4 b = *reinterpret_cast<const float4*>(partial + ((size_t)s * M + m) * N + n);
+      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    }
+    const uint2 pk = make_uint2(pack2(a.x, a.y), pack2(a.z, a.w));
+    *reinterpret_cast<uint2*>(out + (long)m * ldc + n) = pk;
+    acc_stats(pk, true, ss, qq);
+  }
+  *reinterpret_cast<float4*>(stats + (size_t)c * 2 * N + n) = ss;
+  *reinterpret_cast<float4*>(stats + (size_t)c * 2 * N + N + n) = qq;
+}
+
+// sum[n] / sq[n] = the f32 statistics rows of `stats` ([row][sum N | sq N]) added in f64 in a fixed order (deterministic, no atomics):
+// a workgroup owns 64 channels, its 4 waves take every 4th row, the 4 partial sums are added in wave order
+__global__ __launch_bounds__(256) void k_stats_combine(const float* __restrict__ stats, int rows, int N, double* __restrict__ sum, double* __restrict__ sq) {
+  __shared__ double red[2][4][64];
+  const int c = threadIdx.x & 63, part = threadIdx.x >> 6, n = blockIdx.x * 64 + c;
+  double a = 0.0, b = 0.0;
+  if (n < N) {
+#pragma unroll 4
+    for (int r = part; r < rows; r += 4) {
+      a += (double)stats[(size_t)r * 2 * N + n];
+      b += (double)stats[(size_t)r * 2 * N + N + n];
+    }
+  }
+  red[0][part][c] = a;
+  red[1][part][c] = b;
+  __syncthreads();
+  if (part == 0 && n < N) {
+    sum[n] = ((red[0][0][c] + red[0][1][c]) + red[0][2][c]) + red[0][3][c];
+    sq[n] = ((red[1][0][c] + red[1][1][c]) + red[1][2][c]) + red[1][3][c];
+  }
+}
+
+// column statistics of a bf16 matrix: a workgroup owns 8 channels; thread t sums rows t, t + 256, ... in f32, the 256 partial sums are
+// added in f64 by a fixed LDS tree
+__global__ __launch_bounds__(256) void k_colstats_bf16(const unsigned short* __restrict__ x, int ldx, int M, int C, double* __restrict__ sum, double* __restrict__ sq) {
+  __shared__ double red[2][8][256];
+  const int c0 = blockIdx.x * 8, t = threadIdx.x;
+  float s[8], q[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { s[k] = 0.f; q[k] = 0.f; }
+  for (int m = t; m < M; m += 256) {
+    const uint4 v = *reinterpret_cast<const uint4*>(x + (long)m * ldx + c0);
+    const float f[8] = {bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y), bf_lo(v.z), bf_hi(v.z), bf_lo(v.w), bf_hi(v.w)};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { s[k] += f[k]; q[k] = fmaf(f[k], f[k], q[k]); }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { red[0][k][t] = s[k]; red[1][k][t] = q[k]; }
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { red[0][k][t] += red[0][k][t + h]; red[1][k][t] += red[1][k][t + h]; }
+    __syncthreads();
+  }
+  if (t < 8 && c0 + t < C) { sum[c0 + t] = red[0][t][0]; sq[c0 + t] = red[1][t][0]; }
+}
+
 // ---------------------------------------------------------------------------------------------
 // helper kernels (HBM bound)
 // ---------------------------------------------------------------------------------------------
@@ -1020,6 +1153,14 @@ int launch_trans_pool_bf16(const void* X, int ldx, const float* sc, const float*
   return 0;
 }
 
+int launch_colstats_bf16(const void* x, int ldx, int M, int C, double* sum, double* sq, hipStream_t s) {
+  RDM_CHECK_ARG(x && sum && sq && M > 0 && C > 0 && C % 8 == 0 && ldx % 8 == 0 && ldx >= C && ((uintptr_t)x & 15) == 0,
+                "colstats_bf16: C and ldx must be multiples of 8, x 16-byte aligned");
+  hipLaunchKernelGGL(k_colstats_bf16, dim3(C / 8), dim3(256), 0, s, static_cast<const unsigned short*>(x), ldx, M, C, sum, sq);
+  RDM_LAUNCH_OK();
+  return 0;
+}
+
 int launch_gemm_bf16(const GemmBf16Args& a_in, bool out_f32, hipStream_t s) {
   GemmBf16Args a = a_in;
   RDM_CHECK_ARG(a.K > 0 && a.K % 8 == 0 && a.ldx % 8 == 0 && a.ldw % 8 == 0, "gemm_bf16: K (%d) and the row strides must be multiples of 8", a.K);
@@ -1027,6 +1168,9 @@ int launch_gemm_bf16(const GemmBf16Args& a_in, bool out_f32, hipStream_t s) {
   RDM_CHECK_ARG((((uintptr_t)a.X | (uintptr_t)a.W | (uintptr_t)a.out) & 15) == 0, "gemm_bf16: operands must be 16-byte aligned");
   RDM_CHECK_ARG((a.scale == nullptr) == (a.shift == nullptr) && (((uintptr_t)a.scale | (uintptr_t)a.shift | (uintptr_t)a.bias) & 15) == 0, "gemm_bf16: bad prologue / bias pointers");
   RDM_CHECK_ARG((a.oscale == nullptr) == (a.oshift == nullptr) && (((uintptr_t)a.oscale | (uintptr_t)a.oshift) & 15) == 0 && !(a.oscale && out_f32), "gemm_bf16: bad output-activation pointers");
+  const bool stats = a.osum != nullptr;
+  RDM_CHECK_ARG(!stats || (a.osq && a.stats && !out_f32 && !a.oscale && a.stats_floats >= bf16_stats_floats(a.M, a.N) && ((uintptr_t)a.stats & 15) == 0),
+                "gemm_bf16: the statistics epilogue needs osq, a 16-byte aligned stats scratch of bf16_stats_floats(M, N) floats, bf16 output and no output activation");
   const long xb = ((long)(a.M - 1) * a.ldx + a.K) * 2, wb = ((long)(a.N - 1) * a.ldw + a.K) * 2;
   if (xb >= 0xFFFFFFFFL || wb >= 0xFFFFFFFFL) { set_error("gemm_bf16: operand extent >= 4 GiB"); return RDM_ERR_UNSUPPORTED; }
   a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb; a.p_bytes = (unsigned)(a.K * 4);
@@ -1052,7 +1196,9 @@ int launch_gemm_bf16(const GemmBf16Args& a_in, bool out_f32, hipStream_t s) {
 #define RDM_G(MT_, NT_, WM_, WN_, BK_, NS_)                                                                                               \
   do {                                                                                                                                      \
     dim3 grid(cdiv(a.N, NT_ * 16 * WN_), cdiv(a.M, MT_ * 16 * WM_), split);                                                                 \
-    if (out_f32) hipLaunchKernelGGL((gemm_bf16_kernel<MT_, NT_, WM_, WN_, BK_, NS_, true>), grid, dim3(256), 0, s, a);                      \
+    stat_rows = cdiv(a.M, MT_ * 16 * WM_) * WM_;                                                                                            \
+    if (stats) hipLaunchKernelGGL((gemm_bf16_kernel<MT_, NT_, WM_, WN_, BK_, NS_, false, true>), grid, dim3(256), 0, s, a);                 \
+    else if (out_f32) hipLaunchKernelGGL((gemm_bf16_kernel<MT_, NT_, WM_, WN_, BK_, NS_, true>), grid, dim3(256), 0, s, a);                 \
     else hipLaunchKernelGGL((gemm_bf16_kernel<MT_, NT_, WM_, WN_, BK_, NS_, false>), grid, dim3(256), 0, s, a);                             \
     RDM_CENSUS("gemm_bf16_kernel/%dx%d%s", MT_ * 16 * WM_, NT_ * 16 * WN_, split > 1 ? "/splitK" : "");                                     \
   } while (0)
@@ -1063,7 +1209,8 @@ int launch_gemm_bf16(const GemmBf16Args& a_in, bool out_f32, hipStream_t s) {
   a.abl = g_variant >= 200 && g_variant < 216 ? g_variant - 200 : 0;
 #endif
   // (at dense_e3's 525 items - two per workgroup - it only ties the tiled kernel: 37.3 vs 37.0 us at K = 336)
-  const bool panel = !out_f32 && !a.bias && split == 1 && a.K <= 352 && a.M >= 8192 && a.N >= 1024 && (long)cdiv(a.M, 256) * cdiv(a.N, 96) >= 1024;
+  int stat_rows = 0;
+  const bool panel = !stats && !out_f32 && !a.bias && split == 1 && a.K <= 352 && a.M >= 8192 && a.N >= 1024 && (long)cdiv(a.M, 256) * cdiv(a.N, 96) >= 1024;
   void* tk = profile_begin(s, 2.0 * a.M * a.N * (double)a.K, panel ? 11 : 7, 2.0 * ((double)a.M * a.K + (double)a.N * a.K) + (double)a.M * a.N * (out_f32 ? 4 : 2));
   if (panel) {
     // per call, for the CURRENT device (a process may drive several GPUs, from several threads): the attribute query is a cached host-side lookup
@@ -1088,11 +1235,16 @@ int launch_gemm_bf16(const GemmBf16Args& a_in, bool out_f32, hipStream_t s) {
   else if ((long)cdiv(a.M, 128) * cdiv(a.N, 48) >= 512) RDM_G(2, 3, 4, 1, 64, 2);
   else if (a.M > 1024) RDM_G(2, 3, 2, 2, 64, 2);                         // 64 x 96
   else RDM_G(1, 3, 2, 2, 64, 2);                                         // 32 x 96
-  if (split > 1) {
+  if (split > 1 && stats) {
+    stat_rows = cdiv(a.M, RED_ROWS);
+    hipLaunchKernelGGL(k_reduce_partials_stats_bf16, dim3(cdiv((long)stat_rows * (a.N / 4), 256)), dim3(256), 0, s, a.partial, split, a.M, a.N,
+                       static_cast<unsigned short*>(a.out), a.ldc, a.stats);
+  } else if (split > 1) {
     const long mn4 = (long)a.M * a.N / 4;
     hipLaunchKernelGGL(k_reduce_partials_bf16, dim3((unsigned)std::min<long>(cdiv(mn4, 256), 4096)), dim3(256), 0, s, a.partial, split, mn4, a.N / 4,
                        static_cast<unsigned short*>(a.out), a.ldc, a.oscale, a.oshift);
   }
+  if (stats) hipLaunchKernelGGL(k_stats_combine, dim3(cdiv(a.N, 64)), dim3(256), 0, s, a.stats, stat_rows, a.N, a.osum, a.osq);
 #undef RDM_G
   profile_end(tk, s);
   RDM_LAUNCH_OK();
@@ -1104,6 +1256,9 @@ int launch_conv3x3_bf16(const Conv3Bf16Args& a_in, hipStream_t s) {
   RDM_CHECK_ARG(a.C > 0 && a.C % 8 == 0 && a.ldy % 8 == 0 && a.ldw % 8 == 0 && a.wtap % 8 == 0 && a.ldc % 4 == 0, "conv3x3_bf16: C (%d) and the strides must be multiples of 8", a.C);
   RDM_CHECK_ARG((((uintptr_t)a.Y | (uintptr_t)a.Wt | (uintptr_t)a.scale | (uintptr_t)a.shift) & 15) == 0 && ((uintptr_t)a.out & 7) == 0, "conv3x3_bf16: operands must be 16-byte aligned");
   RDM_CHECK_ARG((a.scale == nullptr) == (a.shift == nullptr) && a.M == a.B * a.H * a.W, "conv3x3_bf16: scale and shift come together; M must be B*H*W");
+  const bool stats = a.osum != nullptr;
+  RDM_CHECK_ARG(!stats || (a.osq && a.stats && a.stats_floats >= bf16_stats_floats(a.M, 48) && ((uintptr_t)a.stats & 15) == 0),
+                "conv3x3_bf16: the statistics epilogue needs osq and a 16-byte aligned stats scratch of bf16_stats_floats(M, 48) floats");
   const long yb = ((long)(a.M - 1) * a.ldy + a.C) * 2, wb = (8L * a.wtap + 47L * a.ldw + a.C) * 2;
   if (yb >= 0xFFFFFFFFL || wb >= 0xFFFFFFFFL) { set_error("conv3x3_bf16: operand extent >= 4 GiB"); return RDM_ERR_UNSUPPORTED; }
   a.y_bytes = (unsigned)yb; a.w_bytes = (unsigned)wb; a.p_bytes = (unsigned)(a.C * 4);
@@ -1148,8 +1303,13 @@ int launch_conv3x3_bf16(const Conv3Bf16Args& a_in, hipStream_t s) {
   dim3 grid(tiles, split);
 #define RDM_C3(MT_, HL_)                                                                                                                  \
   do {                                                                                                                                     \
-    if (ldsb > 65536) RDM_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_kernel<MT_, HL_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)); \
-    hipLaunchKernelGGL((conv3x3_bf16_kernel<MT_, HL_>), grid, dim3(256), ldsb, s, a);                                                       \
+    if (stats) {                                                                                                                           \
+      if (ldsb > 65536) RDM_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_kernel<MT_, HL_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)); \
+      hipLaunchKernelGGL((conv3x3_bf16_kernel<MT_, HL_, true>), grid, dim3(256), ldsb, s, a);                                              \
+    } else {                                                                                                                               \
+      if (ldsb > 65536) RDM_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_kernel<MT_, HL_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)); \
+      hipLaunchKernelGGL((conv3x3_bf16_kernel<MT_, HL_>), grid, dim3(256), ldsb, s, a);                                                     \
+    }                                                                                                                                      \
   } while (0)
 #define RDM_C3M(MT_)                                                          \
   do {                                                                        \
@@ -1157,12 +1317,18 @@ int launch_conv3x3_bf16(const Conv3Bf16Args& a_in, hipStream_t s) {
     else RDM_C3(MT_, 20);                                                     \
   } while (0)
   if (bm == 256) RDM_C3M(4); else if (bm == 128) RDM_C3M(2); else RDM_C3M(1);
+  if (stats) RDM_CENSUS("conv3x3_bf16_kernel/%d/stats%s", bm, split > 1 ? "/splitK" : "");     // (the training form only: the eval launches record nothing, as before)
 #undef RDM_C3M
 #undef RDM_C3
-  if (split > 1) {
+  int stat_rows = tiles * 4;                                              // one statistics row per wave
+  if (split > 1 && stats) {
+    stat_rows = cdiv(a.M, RED_ROWS);
+    hipLaunchKernelGGL(k_reduce_partials_stats_bf16, dim3(cdiv((long)stat_rows * 12, 256)), dim3(256), 0, s, a.partial, split, a.M, 48, a.out, a.ldc, a.stats);
+  } else if (split > 1) {
     const long mn4 = (long)a.M * 12;
     hipLaunchKernelGGL(k_reduce_partials_bf16, dim3((unsigned)std::min<long>(cdiv(mn4, 256), 4096)), dim3(256), 0, s, a.partial, split, mn4, 12, a.out, a.ldc, nullptr, nullptr);
   }
+  if (stats) hipLaunchKernelGGL(k_stats_combine, dim3(1), dim3(256), 0, s, a.stats, stat_rows, 48, a.osum, a.osq);
   profile_end(tk, s);
   RDM_LAUNCH_OK();
   return 0;

@@ -908,6 +908,38 @@ int dense_block_bf16(const DenseBf16Block& d, hipStream_t s) {
   return RDM_OK;
 }
 
+/* the training form of dense_block_bf16 (bf16.h DenseBf16TrainBlock): the 1x1 cannot apply norm2 in its epilogue (its affine comes from
+ * the 1x1's own output), so it stores the raw bottleneck with its statistics and the 3x3 applies norm2 in its prologue. */
+int dense_block_bf16_train(const DenseBf16TrainBlock& d, hipStream_t s) {
+  int rc;
+  RDM_CHECK_ARG(d.layers > 0 && d.layers <= 48 && d.cin0 + d.layers * GROWTH <= d.ctot, "dense block: 1..48 layers within ctot");
+  const double count = (double)d.M;
+  for (int i = 0; i < d.layers; ++i) {
+    const int cin = d.cin0 + i * GROWTH;
+    float* a1 = d.aff1;                                              // scale | shift | mean | rstd of [0, cin), row stride cin
+    if ((rc = launch_bn_finalize(d.bsum, d.bsq, count, d.g1[i], d.b1[i], d.rm1[i], d.rv1[i], d.nbt1[i], a1, a1 + cin, a1 + 2 * cin, a1 + 3 * cin, cin, 1, s)))
+      return rc;
+    GemmBf16Args a{};
+    a.X = d.blk; a.ldx = d.ctot; a.K = cin; a.scale = a1; a.shift = a1 + cin;
+    a.W = d.w1[i]; a.ldw = cin;
+    a.out = d.Y; a.ldc = d.cb; a.M = d.M; a.N = d.cb;
+    a.partial = d.partial; a.partial_floats = d.partial_floats;
+    a.osum = d.ysum; a.osq = d.ysq; a.stats = d.stats; a.stats_floats = d.stats_floats;
+    if ((rc = launch_gemm_bf16(a, false, s))) return rc;
+    float* a2 = d.aff2;
+    if ((rc = launch_bn_finalize(d.ysum, d.ysq, count, d.g2[i], d.b2[i], d.rm2[i], d.rv2[i], d.nbt2[i], a2, a2 + d.cb, a2 + 2 * d.cb, a2 + 3 * d.cb, d.cb, 1, s)))
+      return rc;
+    Conv3Bf16Args c{};
+    c.Y = d.Y; c.ldy = d.cb; c.C = d.cb; c.scale = a2; c.shift = a2 + d.cb;
+    c.Wt = d.w3[i]; c.wtap = (long)GROWTH * d.cb; c.ldw = d.cb;
+    c.out = d.blk + cin; c.ldc = d.ctot; c.B = d.B; c.H = d.H; c.W = d.W; c.M = d.M;
+    c.partial = d.partial; c.partial_floats = d.partial_floats;
+    c.osum = d.bsum + cin; c.osq = d.bsq + cin; c.stats = d.stats; c.stats_floats = d.stats_floats;
+    if ((rc = launch_conv3x3_bf16(c, s))) return rc;
+  }
+  return RDM_OK;
+}
+
 }  // namespace rdm
 
 using namespace rdm;

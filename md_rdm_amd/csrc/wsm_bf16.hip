@@ -339,6 +339,7 @@ struct RelPlan {
   RelWsm L[4];
   size_t c1_w, c1_b, wbytes = 0;
   size_t blk, Y, partial, partial_floats, wsbytes = 0;
+  size_t bst, yst, aff1, aff2, stats, stats_floats, train_wsbytes = 0;    // training form (plan_rel_train): behind the eval layout
 };
 
 static size_t take(size_t& off, size_t bytes) {
@@ -389,6 +390,20 @@ static void plan_rel(int id, int B, RelPlan& P) {
   P.wsbytes = a;
 }
 
+// the training forward's extra workspace, appended to the eval layout (which stays as it is): block / bottleneck statistics (f64),
+// BatchNorm affines, the statistics epilogues' f32 scratch
+static void plan_rel_train(RelPlan& P) {
+  size_t a = P.wsbytes;
+  const int M8 = P.B * 64;
+  P.bst = take(a, (size_t)2 * kCtot * 8);
+  P.yst = take(a, (size_t)2 * kCb * 8);
+  P.aff1 = take(a, (size_t)4 * kCtot * 4);
+  P.aff2 = take(a, (size_t)4 * kCb * 4);
+  P.stats_floats = bf16_stats_floats(M8, kCb);
+  P.stats = take(a, P.stats_floats * 4);
+  P.train_wsbytes = a;
+}
+
 template <class T> static T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
 static const float* Fp(void* const* T, int i) { return static_cast<const float*>(T[i]); }
 
@@ -396,6 +411,71 @@ static const float* Fp(void* const* T, int i) { return static_cast<const float*>
 // wsm_block.WSM_k (deconv1.0 w b, conv1_1..conv1_5 w b, conv2_1 w b, conv2_2 w b, wsm_wx3.1 w b, wsm_3xh.1 w b, input_adjustment_layer w b),
 // conv1 w b, conv2 w b
 static int rel_num_tensors(int id) { return 12 * kLayers + 22 * (id - 6) + 4; }
+
+// WSM chain + conv1 of a relative decoder (RDM_Net.py:151-157) from the finished dense block in the workspace: no BatchNorm, so the eval
+// and the training forward enqueue the same launches
+static int rel_wsm_chain(const RelPlan& P, int batch, void* wb, void* ws, float* out_map, hipStream_t s) {
+  int rc;
+  const int M8 = batch * 64;
+  unsigned short* blk = at<unsigned short>(ws, P.blk);
+  const void* x = blk;
+  long x_elems = (long)M8 * kCtot;
+  int ldx = kCtot;
+  for (int l = 0; l < P.nw; ++l) {
+    const RelWsm& R = P.L[l];
+    const int h = R.S / 2, S = R.S, C = R.C;
+    const long Mo = (long)batch * S * S;
+    unsigned short* t = at<unsigned short>(ws, R.t);
+    unsigned short* out1 = at<unsigned short>(ws, R.out1);
+    unsigned short* Tt = at<unsigned short>(ws, R.T);
+    unsigned short* out = at<unsigned short>(ws, R.out);
+    const int ldT = R.nf - R.kip;
+    {  // input_adjustment_layer: 1x1 raw -> C (+bias), all cp columns (the pad columns are exact zeros)
+      WsmConvArgs a = conv_args(x, x_elems, ldx, 0, R.raw, batch, h, h, 1, at<char>(wb, R.ia_w), R.cp, at<float>(wb, R.ia_b), R.cp);
+      a.nseg = 1; a.seg[0] = seg(t, 0, R.cp, R.cp, R.cp, 0, WSM_PLAIN);
+      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+    }
+    {  // deconv1: 1x1 to 4 phases x cp, stored through the pixel shuffle
+      WsmConvArgs a = conv_args(t, (long)batch * h * h * R.cp, R.cp, 0, R.cp, batch, h, h, 1, at<char>(wb, R.dc_w), 4 * R.cp, at<float>(wb, R.dc_b), 4 * R.cp);
+      a.nseg = 1; a.seg[0] = seg(out1, 0, 4 * R.cp, R.cp, R.cp, 0, WSM_SHUFFLE);
+      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+    }
+    {  // conv1_1..conv1_5 as ONE GEMM: conv1_1 -> its slot of the output, the other four -> the scratch T
+      WsmConvArgs a = conv_args(out1, Mo * R.cp, R.cp, 0, R.cp, batch, S, S, 1, at<char>(wb, R.f5_w), R.nf, at<float>(wb, R.f5_b), R.nf);
+      a.nseg = 2;
+      a.seg[0] = seg(out, 0, R.kip, R.ki, C, 0, WSM_PLAIN);
+      a.seg[1] = seg(Tt, R.kip, R.nf, ldT, ldT, 0, WSM_PLAIN);
+      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+    }
+    {  // conv2_1 3x3 p1 on out1_2 -> slot 1
+      WsmConvArgs a = conv_args(Tt, Mo * ldT, ldT, 0, R.kip, batch, S, S, 3, at<char>(wb, R.c3_w), R.ki, at<float>(wb, R.c3_b), R.ki);
+      a.nseg = 1; a.seg[0] = seg(out, 0, R.kip, R.ki, C, R.ki, WSM_PLAIN);
+      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+    }
+    {  // conv2_2 5x5 p2 on out1_3 -> slot 2
+      WsmConvArgs a = conv_args(Tt, Mo * ldT, ldT, R.kip, R.kip, batch, S, S, 5, at<char>(wb, R.c5_w), R.ki, at<float>(wb, R.c5_b), R.ki);
+      a.nseg = 1; a.seg[0] = seg(out, 0, R.kip, R.ki, C, 2 * R.ki, WSM_PLAIN);
+      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+    }
+    {  // wsm_3xh on out1_5: one value per COLUMN, repeated along H -> completion_vertical, slot 3
+      WsmConvArgs a = strip_args(Tt, Mo * ldT, ldT, 2 * R.kip + R.wip, R.wip, batch, S, true, at<char>(wb, R.sh_w), R.wi, at<float>(wb, R.sh_b), R.wi);
+      a.nseg = 1; a.seg[0] = seg(out, 0, R.wip, R.wi, C, 3 * R.ki, WSM_BCAST_COLS);
+      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+    }
+    {  // wsm_wx3 on out1_4: one value per ROW, repeated along W -> completion_horizontal, slot 4
+      WsmConvArgs a = strip_args(Tt, Mo * ldT, ldT, 2 * R.kip, R.wip, batch, S, false, at<char>(wb, R.sv_w), R.wi, at<float>(wb, R.sv_b), R.wi);
+      a.nseg = 1; a.seg[0] = seg(out, 0, R.wip, R.wi, C, 3 * R.ki + R.wi, WSM_BCAST_ROWS);
+      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+    }
+    x = out; x_elems = Mo * C; ldx = C;
+  }
+  {  // conv1: 1x1 -> 1 channel + bias, f32 (B,1,S,S) (NCHW with one channel == NHWC)
+    WsmConvArgs a = conv_args(x, x_elems, ldx, 0, P.cf, batch, P.sf, P.sf, 1, at<char>(wb, P.c1_w), 1, at<float>(wb, P.c1_b), 1);
+    a.nseg = 1; a.seg[0] = seg(out_map, 0, 4, 1, 1, 0, WSM_F32);
+    if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+  }
+  return RDM_OK;
+}
 
 }  // namespace rdm
 
@@ -506,63 +586,64 @@ int rdm_rel_forward_bf16(int32_t id, const void* enc, int32_t ld_enc, int32_t ba
     }
     if ((rc = dense_block_bf16(d, s))) return rc;
   }
-  const void* x = blk;
-  long x_elems = (long)M8 * kCtot;
-  int ldx = kCtot;
-  for (int l = 0; l < P.nw; ++l) {
-    const RelWsm& R = P.L[l];
-    const int h = R.S / 2, S = R.S, C = R.C;
-    const long Mo = (long)batch * S * S;
-    unsigned short* t = at<unsigned short>(ws, R.t);
-    unsigned short* out1 = at<unsigned short>(ws, R.out1);
-    unsigned short* Tt = at<unsigned short>(ws, R.T);
-    unsigned short* out = at<unsigned short>(ws, R.out);
-    const int ldT = R.nf - R.kip;
-    {  // input_adjustment_layer: 1x1 raw -> C (+bias), all cp columns (the pad columns are exact zeros)
-      WsmConvArgs a = conv_args(x, x_elems, ldx, 0, R.raw, batch, h, h, 1, at<char>(wb, R.ia_w), R.cp, at<float>(wb, R.ia_b), R.cp);
-      a.nseg = 1; a.seg[0] = seg(t, 0, R.cp, R.cp, R.cp, 0, WSM_PLAIN);
-      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
-    }
-    {  // deconv1: 1x1 to 4 phases x cp, stored through the pixel shuffle
-      WsmConvArgs a = conv_args(t, (long)batch * h * h * R.cp, R.cp, 0, R.cp, batch, h, h, 1, at<char>(wb, R.dc_w), 4 * R.cp, at<float>(wb, R.dc_b), 4 * R.cp);
-      a.nseg = 1; a.seg[0] = seg(out1, 0, 4 * R.cp, R.cp, R.cp, 0, WSM_SHUFFLE);
-      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
-    }
-    {  // conv1_1..conv1_5 as ONE GEMM: conv1_1 -> its slot of the output, the other four -> the scratch T
-      WsmConvArgs a = conv_args(out1, Mo * R.cp, R.cp, 0, R.cp, batch, S, S, 1, at<char>(wb, R.f5_w), R.nf, at<float>(wb, R.f5_b), R.nf);
-      a.nseg = 2;
-      a.seg[0] = seg(out, 0, R.kip, R.ki, C, 0, WSM_PLAIN);
-      a.seg[1] = seg(Tt, R.kip, R.nf, ldT, ldT, 0, WSM_PLAIN);
-      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
-    }
-    {  // conv2_1 3x3 p1 on out1_2 -> slot 1
-      WsmConvArgs a = conv_args(Tt, Mo * ldT, ldT, 0, R.kip, batch, S, S, 3, at<char>(wb, R.c3_w), R.ki, at<float>(wb, R.c3_b), R.ki);
-      a.nseg = 1; a.seg[0] = seg(out, 0, R.kip, R.ki, C, R.ki, WSM_PLAIN);
-      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
-    }
-    {  // conv2_2 5x5 p2 on out1_3 -> slot 2
-      WsmConvArgs a = conv_args(Tt, Mo * ldT, ldT, R.kip, R.kip, batch, S, S, 5, at<char>(wb, R.c5_w), R.ki, at<float>(wb, R.c5_b), R.ki);
-      a.nseg = 1; a.seg[0] = seg(out, 0, R.kip, R.ki, C, 2 * R.ki, WSM_PLAIN);
-      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
-    }
-    {  // wsm_3xh on out1_5: one value per COLUMN, repeated along H -> completion_vertical, slot 3
-      WsmConvArgs a = strip_args(Tt, Mo * ldT, ldT, 2 * R.kip + R.wip, R.wip, batch, S, true, at<char>(wb, R.sh_w), R.wi, at<float>(wb, R.sh_b), R.wi);
-      a.nseg = 1; a.seg[0] = seg(out, 0, R.wip, R.wi, C, 3 * R.ki, WSM_BCAST_COLS);
-      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
-    }
-    {  // wsm_wx3 on out1_4: one value per ROW, repeated along W -> completion_horizontal, slot 4
-      WsmConvArgs a = strip_args(Tt, Mo * ldT, ldT, 2 * R.kip, R.wip, batch, S, false, at<char>(wb, R.sv_w), R.wi, at<float>(wb, R.sv_b), R.wi);
-      a.nseg = 1; a.seg[0] = seg(out, 0, R.wip, R.wi, C, 3 * R.ki + R.wi, WSM_BCAST_ROWS);
-      if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
-    }
-    x = out; x_elems = Mo * C; ldx = C;
+  return rel_wsm_chain(P, batch, wb, ws, out_map, s);
+}
+
+size_t rdm_rel_bf16_train_workspace_bytes(int32_t id, int32_t batch) {
+  if (id < 6 || id > 10 || batch <= 0) return 0;
+  RelPlan P;
+  plan_rel(id, batch, P);
+  plan_rel_train(P);
+  return P.train_wsbytes;
+}
+
+int rdm_rel_forward_bf16_train(int32_t id, const void* enc, int32_t ld_enc, const double* enc_stats, int32_t batch, void* const* T, const void* wbuf, void* ws,
+                               size_t ws_bytes, float* out_map, rdm_stream_t stream) {
+  RDM_CHECK_ARG(id >= 6 && id <= 10, "relative decoder id must be 6..10, got %d", id);
+  RDM_CHECK_ARG(enc && T && wbuf && ws && out_map, "NULL argument");
+  RDM_CHECK_ARG(batch > 0 && batch <= 256 && ld_enc >= kCin0 && ld_enc % 8 == 0, "batch must be 1..256 (32-bit buffer offsets), ld_enc >= 1056 and a multiple of 8");
+  RDM_CHECK_ARG((((uintptr_t)ws | (uintptr_t)wbuf) & 255) == 0 && ((uintptr_t)enc & 15) == 0, "workspace and weight buffer must be 256-byte aligned, enc 16-byte aligned");
+  RelPlan P;
+  plan_rel(id, batch, P);
+  plan_rel_train(P);
+  if (ws_bytes < P.train_wsbytes) { set_error("relative decoder training workspace too small: %zu < %zu", ws_bytes, P.train_wsbytes); return RDM_ERR_WORKSPACE_TOO_SMALL; }
+  for (int i = 0; i < 12 * kLayers; ++i) RDM_CHECK_ARG(T[i] != nullptr, "tensor %d is NULL", i);
+  hipStream_t s = stream;
+  void* wb = const_cast<void*>(wbuf);
+  int rc;
+  const int M8 = batch * 64;
+  unsigned short* blk = at<unsigned short>(ws, P.blk);
+  double* bst = at<double>(ws, P.bst);
+  RDM_HIP_OK(hipMemcpy2DAsync(blk, (size_t)kCtot * 2, enc, (size_t)ld_enc * 2, (size_t)kCin0 * 2, M8, hipMemcpyDeviceToDevice, s));
+  if (enc_stats) {                                                   // [sum 1056 | sq 1056], shared by the decoders of one forward
+    RDM_HIP_OK(hipMemcpyAsync(bst, enc_stats, (size_t)kCin0 * 8, hipMemcpyDeviceToDevice, s));
+    RDM_HIP_OK(hipMemcpyAsync(bst + kCtot, enc_stats + kCin0, (size_t)kCin0 * 8, hipMemcpyDeviceToDevice, s));
+  } else if ((rc = launch_colstats_bf16(enc, ld_enc, M8, kCin0, bst, bst + kCtot, s))) {
+    return rc;
   }
-  {  // conv1: 1x1 -> 1 channel + bias, f32 (B,1,S,S) (NCHW with one channel == NHWC)
-    WsmConvArgs a = conv_args(x, x_elems, ldx, 0, P.cf, batch, P.sf, P.sf, 1, at<char>(wb, P.c1_w), 1, at<float>(wb, P.c1_b), 1);
-    a.nseg = 1; a.seg[0] = seg(out_map, 0, 4, 1, 1, 0, WSM_F32);
-    if ((rc = launch_wsm_conv_bf16(a, s))) return rc;
+  {
+    DenseBf16TrainBlock d{};
+    d.blk = blk; d.B = batch; d.H = 8; d.W = 8; d.M = M8; d.ctot = kCtot; d.cin0 = kCin0; d.layers = kLayers; d.cb = kCb;
+    d.Y = at<char>(ws, P.Y); d.partial = at<float>(ws, P.partial); d.partial_floats = P.partial_floats;
+    d.stats = at<float>(ws, P.stats); d.stats_floats = P.stats_floats;
+    d.bsum = bst; d.bsq = bst + kCtot;
+    d.ysum = at<double>(ws, P.yst); d.ysq = d.ysum + kCb;
+    d.aff1 = at<float>(ws, P.aff1); d.aff2 = at<float>(ws, P.aff2);
+    for (int i = 0; i < kLayers; ++i) {
+      const int b = 12 * i;                                          // norm1 w b rm rv nbt, conv1, norm2 w b rm rv nbt, conv2
+      d.w1[i] = at<char>(wb, P.dw1[i]); d.w3[i] = at<char>(wb, P.dw3[i]);
+      d.g1[i] = Fp(T, b); d.b1[i] = Fp(T, b + 1); d.rm1[i] = static_cast<float*>(T[b + 2]); d.rv1[i] = static_cast<float*>(T[b + 3]);
+      d.nbt1[i] = static_cast<long long*>(T[b + 4]);
+      d.g2[i] = Fp(T, b + 6); d.b2[i] = Fp(T, b + 7); d.rm2[i] = static_cast<float*>(T[b + 8]); d.rv2[i] = static_cast<float*>(T[b + 9]);
+      d.nbt2[i] = static_cast<long long*>(T[b + 10]);
+    }
+    if ((rc = dense_block_bf16_train(d, s))) return rc;
   }
-  return RDM_OK;
+  return rel_wsm_chain(P, batch, wb, ws, out_map, s);
+}
+
+int rdm_colstats_bf16(const void* x, int32_t ldx, int32_t m, int32_t c, double* sum, double* sumsq, rdm_stream_t stream) {
+  return launch_colstats_bf16(x, ldx, m, c, sum, sumsq, stream);
 }
 
 int rdm_rel_bf16_input_nchw(const float* x_nchw, int32_t batch, void* enc, int32_t ld_enc, rdm_stream_t stream) {

@@ -142,7 +142,7 @@ class FusedAdamW:
         else:
             for a, b in self.trainable_ranges():                  # 2 launches for the reference's live graph (around d_1.conv1)
                 self._update(a, b, grad_scale)
-        self.model.mark_weights_changed()                         # derived bf16 copies are stale now
+        self.model.mark_weights_changed(relative_decoders=False)  # derived bf16 copies are stale now (d_6..d_10 are not in the flat buffer: untouched)
         self.small.step()
 
     def state_dict(self):

@@ -230,18 +230,21 @@ class Decoder(nn.Module):
         self.precision = precision
         return self
 
+    # Two staleness flags: _bf16_rel_stale (the eval path: weights or running statistics changed) and _bf16_rel_wstale (the training path
+    # reads only the packed conv weights: weights changed).  A training forward moves the running statistics, so it sets the first only.
     def mark_weights_changed(self):
         self._bf16_rel_stale = True
+        self._bf16_rel_wstale = True
 
     def load_state_dict(self, *a, **k):
-        self._bf16_rel_stale = True
+        self.mark_weights_changed()
         return super().load_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):
-        self._bf16_rel_stale = True
+        self.mark_weights_changed()
         return super()._apply(fn, *a, **k)
 
-    def _prepare_bf16(self, device):
+    def _prepare_bf16(self, device, weights_only=False):
         L = _lib.lib()
         tensors = list(self.state_dict().values())
         if len(tensors) != L.rdm_rel_num_tensors(self.id):
@@ -251,11 +254,34 @@ class Decoder(nn.Module):
         if w is None or w.numel() < nbytes or w.device != device:
             w = self.__dict__["_bf16_rel_w"] = torch.empty(nbytes, dtype=torch.uint8, device=device)
             self._bf16_rel_stale = True
-        if self.__dict__.get("_bf16_rel_stale", True):
+            self._bf16_rel_wstale = True
+        if self.__dict__.get("_bf16_rel_wstale" if weights_only else "_bf16_rel_stale", True):
             table = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
             _lib.check(L.rdm_rel_bf16_prepare(self.id, table, C.c_void_p(w.data_ptr()), nbytes, _lib.stream()))
             self._bf16_rel_stale = False
+            self._bf16_rel_wstale = False
         return w
+
+    def features_bf16_train(self, enc, ld_enc, batch, enc_stats=None):
+        """The TRAINING-mode bf16 forward (rdm_rel_forward_bf16_train): enc as ``features_bf16``; BatchNorm from the batch statistics,
+        running statistics updated in place like nn.BatchNorm2d; forward only.  ``enc_stats``: optional (2*1056,) float64 column sums and
+        sums of squares of enc (rdm_colstats_bf16), shared by the decoders of one forward.  (B,1,S,S) f32."""
+        L = _lib.lib()
+        if not self.training:
+            raise _lib.RdmError("features_bf16_train is the training-mode forward (batch-statistics BatchNorm): call train(), or features_bf16 for inference")
+        w = self._prepare_bf16(enc.device, weights_only=True)
+        tensors = list(self.state_dict().values())
+        ws_bytes = int(L.rdm_rel_bf16_train_workspace_bytes(self.id, batch))
+        ws = self.__dict__.get("_bf16_rel_tws")
+        if ws is None or ws.numel() < ws_bytes or ws.device != enc.device:
+            ws = self.__dict__["_bf16_rel_tws"] = torch.empty(ws_bytes, dtype=torch.uint8, device=enc.device)
+        S = 2 ** (self.id - 3)
+        out = torch.empty(batch, 1, S, S, dtype=torch.float32, device=enc.device)
+        table = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        _lib.check(L.rdm_rel_forward_bf16_train(self.id, _lib.ptr(enc), ld_enc, _lib.ptr(enc_stats), batch, table, C.c_void_p(w.data_ptr()),
+                                                C.c_void_p(ws.data_ptr()), ws_bytes, _lib.ptr(out), _lib.stream()))
+        self._bf16_rel_stale = True                     # the running statistics moved: the eval-folded affines are stale (the packed weights are not)
+        return out
 
     def features_bf16(self, enc, ld_enc, batch):
         """The bf16 forward from the encoder output as (batch*8*8, ld_enc) NHWC bf16 (any dtype holding those bytes): (B,1,S,S) f32."""
@@ -393,6 +419,7 @@ class DepthEstimationNet(BaseModel):
                                    # activations, weights, BatchNorm statistics, losses and AdamW stay float32.  Not the parity configuration.
         self.backward_precision = "bf16x3"   # "bf16x3" (default): the gradient GEMMs of dense_e2 / dense_e3 run the split-precision kernels
                                    # (RDM_NET_OPT_SPLIT_BWD, csrc/xsplit.hip: ~5e-6 of a gradient's maximum); "f32": exact-f32 MFMA everywhere
+        self.relative_train_precision = "f32"   # "bf16": the training-mode forward of the relative decoders on the bf16 path (set_relative_train_precision)
         self._bf16_w = None        # prepared bf16 weights + folded BatchNorm affines (rdm_net_bf16_prepare)
         self._bf16_stale = True
         self._bf16_ws = None
@@ -568,13 +595,30 @@ class DepthEstimationNet(BaseModel):
         self.precision = precision
         return self
 
-    def mark_weights_changed(self):
+    def set_relative_train_precision(self, precision):
+        """"f32" (default) or "bf16": the TRAINING-mode forward of the relative decoders (``relative_decoders``).  "bf16" runs their dense
+        blocks, WSM chains and conv1 on the bf16 MFMA kernels (rdm_rel_forward_bf16_train: bf16 conv operands, f32 accumulation, float32
+        BatchNorm from the batch statistics, running statistics updated like nn.BatchNorm2d) - the reference's `--precision 16` treatment of
+        these forward-only decoders.  No effect in eval mode (``set_precision`` decides there); tolerance in tests/test_gpu_relative_bf16_train.py."""
+        if precision not in ("f32", "bf16"):
+            raise ValueError("relative train precision must be 'f32' or 'bf16'")
+        self.relative_train_precision = precision
+        return self
+
+    def mark_weights_changed(self, relative_decoders=True):
         """The bf16 copies are derived data: call after any in-place weight update that bypasses this class (the fused AdamW
-        does it itself; load_state_dict / .to() are caught below)."""
+        does it itself; load_state_dict / .to() are caught below).  The relative decoders' packed weights (the bf16 training forward reads
+        them without passing through prepare_bf16) are marked too, unless the caller knows it changed none of d_6..d_10
+        (``relative_decoders=False``: the fused AdamW, whose update covers the flat buffer and weight_layer only)."""
         self._bf16_stale = True
+        if relative_decoders:
+            for did in self.relative_ids:
+                getattr(self, "d_%d" % did).mark_weights_changed()
 
     def load_state_dict(self, *a, **k):
         self._bf16_stale = True
+        for did in self.relative_ids:                       # (the decoders' own load_state_dict is not called on this path)
+            getattr(self, "d_%d" % did).mark_weights_changed()
         return super().load_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):
@@ -683,14 +727,23 @@ class DepthEstimationNet(BaseModel):
             if (H, W) != (8, 8):
                 raise _lib.RdmError("the relative decoders need the square 8x8 encoder output (226/228-pixel inputs), got %dx%d" % (H, W))
             with torch.no_grad():
+                train_bf16 = not bf16 and self.training and self.relative_train_precision == "bf16"
                 if bf16:                                                         # trans_e4 output as (B*64, 1056) bf16 NHWC, no layout pass
                     enc = self.encoder_output_bf16()
                 else:
                     enc = self.encoder_output()                                  # trans_e4 output (B,1056,8,8) of the forward above
+                if train_bf16:                                                   # converted once, its column statistics taken once: every decoder reads it
+                    L = _lib.lib()
+                    enc16 = torch.empty(B * 64, 1056, dtype=torch.bfloat16, device=enc.device)
+                    _lib.check(L.rdm_rel_bf16_input_nchw(_lib.ptr(enc), B, _lib.ptr(enc16), 1056, _lib.stream()))
+                    enc_stats = torch.empty(2 * 1056, dtype=torch.float64, device=enc.device)
+                    _lib.check(L.rdm_colstats_bf16(_lib.ptr(enc16), 1056, B * 64, 1056, _lib.ptr(enc_stats[:1056]), _lib.ptr(enc_stats[1056:]), _lib.stream()))
                 for did in self.relative_ids:
                     dec = getattr(self, "d_%d" % did)
                     if bf16:
                         x_dk = dec.ord_layer(dec.features_bf16(enc, 1056, B))    # (B,1,S,S) relative map, S = 2^(did-3)
+                    elif train_bf16:
+                        x_dk = dec.ord_layer(dec.features_bf16_train(enc16, 1056, B, enc_stats))
                     else:
                         x_dk = dec(enc)
                     rows.append(cp.decompose_depth_map([], x_dk, did - 3, relative_map=True)[::-1])

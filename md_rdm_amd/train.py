@@ -72,6 +72,8 @@ def main(argv=None):
     parser.add_argument("--checkpoint_dir", type=str, default=None, help="keep the best checkpoint by val_delta1 here (train.py:41-47: ModelCheckpoint(save_top_k=1, monitor='val_delta1', mode='max'))")
     parser.add_argument("--resume", type=str, default=None, help="Lightning .ckpt or state_dict to start from")
     parser.add_argument("--relative_decoders", type=int, nargs="*", default=[], help="subset of 6 7 8 9 10: the relative decoders the reference keeps commented out (RDM_Net.py:57-61)")
+    parser.add_argument("--relative_bf16", action="store_true", help="training-mode forward of the relative decoders (--relative_decoders) on the bf16 MFMA path: bf16 conv operands, "
+                        "float32 BatchNorm from batch statistics (DepthEstimationNet.set_relative_train_precision('bf16')); independent of --precision")
     args = parser.parse_args(argv)
     if args.precision not in (16, 32):
         raise SystemExit("--precision must be 16 or 32")
@@ -109,6 +111,7 @@ def main(argv=None):
     # AdamW steps within 0.1 % (tests/test_gpu_mixed.py).  Mode 1 (forward GEMMs rounded as well: logits RMS 3 %, gradient cosine down to
     # 0.84 at the hash-filled initial point, no loss scaling or long-run convergence evidence) stays an explicit choice: --gemm_bf16 1.
     model.gemm_bf16 = (args.gemm_bf16 if args.gemm_bf16 is not None else 3) if args.precision == 16 else (args.gemm_bf16 or 0)
+    model.set_relative_train_precision("bf16" if args.relative_bf16 else "f32")
     # the reference trains on the GPU, where depth2label_sid of a non-positive depth (int(NaN)) is 0; the CPU semantics (0x80000000) are what
     # the fixtures pin and stay the library default - training follows the reference's device
     from . import utils as _u
