@@ -543,6 +543,20 @@ int rdm_candidates_matvec_bwd(const double* a, const float* dout, float* dw, int
 int rdm_recombine_f64(const float* yhat, double* out, int32_t batch, int32_t n_levels, int32_t n_out, int32_t first_level, rdm_stream_t stream);
 int rdm_recombine_bwd(const double* dout, float* dyhat, int32_t batch, int32_t n_levels, int32_t n_out, int32_t first_level, rdm_stream_t stream);
 
+/* The inference tail in ONE launch for the ordinal-only model with a square power-of-two head (side h == w = 2^n, n <= 4):
+ * RDM_Net.py:313-345 (DORN counts) + RDM_Net.py:117 (geometric-mean normalisation, exponent 1/(h*w), rounded to float32) +
+ * computations.py:368-392 (decompose) + computations.py:512-528 (float32(log F_k) * w[k], one candidate per level) +
+ * computations.py:394-421 (recombination at 2^n_out); optimize_components (computations.py:499-510) returns its predictions unchanged,
+ * so this is the reference's answer for an image.  Same arithmetic, in the same order, as rdm_dorn_fwd -> rdm_gm_normalize_f64 ->
+ * rdm_decompose_f64 -> rdm_fine_detail_pred_f32 -> rdm_recombine_f64; the ordinal probabilities are never written.
+ *   logits (B,2K,h,w) f32 NCHW;  w: n+1 level weights (d0, f1..fn);  log_map (B,1,2^n_out,2^n_out) f64, 16-byte aligned (required);
+ *   decode (B,1,h,w) i64 DORN counts, or NULL;  linear_map (B,1,2^n_out,2^n_out) f32 = exp(log_map), or NULL.
+ * split: workgroups per image, each storing 1/split of the rows (a power of two <= 2^n_out; 0 = the library's measured default); the
+ * result does not depend on it.  No atomics: bit-reproducible.  A non-square or non-power-of-two head returns RDM_ERR_BAD_ARGUMENT and
+ * writes nothing. */
+int rdm_predict_tail_f32(const float* logits, const float* w, double* log_map, int64_t* decode, float* linear_map, int32_t batch, int32_t k, int32_t h,
+                         int32_t wd, int32_t n_out, int32_t split, rdm_stream_t stream);
+
 /* metrics.py:48-128 (validation metrics) in one pass over the pixels with target > 0 (pred clamped to 1e-7):
  * out10 = [count, #delta1, #delta2, #delta3, sum sq err, sum abs err, sum |log10 p - log10 t|,
  *          sum |p-t|/t, sum (p-t)^2/t, sum sqrt((p-t)^2/t)]; the host divides by count (after an all-reduce under DP) */

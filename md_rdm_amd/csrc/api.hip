@@ -15,6 +15,7 @@
 #include "bf16.h"
 #include "wino.h"
 #include "xsplit.h"
+#include "predict.h"
 
 namespace rdm {
 long long g_launches = 0;
@@ -100,6 +101,21 @@ int rdm_profile_kind(int32_t kind, const char** name, double* ms_sum, double* fl
 
 /* algorithmic HBM bytes (operands read once + result written once) of the launches of `kind` in the last rdm_profile_read(); 0 for the f32 kinds */
 double rdm_profile_kind_bytes(int32_t kind) { return profile_kind_bytes(kind); }
+
+int rdm_predict_tail_f32(const float* logits, const float* w, double* log_map, int64_t* decode, float* linear_map, int32_t batch, int32_t k, int32_t h,
+                         int32_t wd, int32_t n_out, int32_t split, rdm_stream_t stream) {
+  RDM_CHECK_ARG(logits && w && log_map, "predict_tail: logits, w and log_map must not be NULL");
+  RDM_CHECK_ARG(batch > 0 && batch <= 65535 && k > 0, "predict_tail: need 0 < batch <= 65535 and k > 0 (got %d, %d)", (int)batch, (int)k);
+  RDM_CHECK_ARG(h > 0 && h == wd, "predict_tail: the fused tail needs a square head, got %dx%d (compose the single operators for other shapes)", (int)h, (int)wd);
+  RDM_CHECK_ARG((h & (h - 1)) == 0 && h <= 16, "predict_tail: head side %d is not a power of two <= 16", (int)h);
+  int n = 0;
+  while ((1 << n) < h) ++n;
+  RDM_CHECK_ARG(n_out >= 1 && n_out >= n && n_out <= 10, "predict_tail: need max(1, log2 side) <= n_out <= 10, got %d", (int)n_out);
+  RDM_CHECK_ARG(split >= 0 && (split & (split - 1)) == 0 && split <= (1 << n_out), "predict_tail: split (%d) must be 0 (default) or a power of two <= 2^n_out", (int)split);
+  RDM_CHECK_ARG(((uintptr_t)log_map & 15) == 0 && ((uintptr_t)linear_map & 7) == 0, "predict_tail: log_map must be 16-byte and linear_map 8-byte aligned");
+  if (split == 0) split = predict_tail_default_split(batch, n_out);
+  return launch_predict_tail(logits, w, log_map, decode, linear_map, batch, k, n, n_out, split, (hipStream_t)stream);
+}
 
 size_t rdm_nyu_preprocess_workspace_bytes(int32_t batch, int32_t in_h, int32_t in_w, int32_t resized_h, int32_t resized_w, int32_t out_w) {
   return nyu_preprocess_workspace_bytes(batch, in_h, in_w, resized_h, resized_w, out_w);

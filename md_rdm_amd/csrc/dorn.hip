@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "rdm_common.h"
+#include "postproc_dev.h"
 
 namespace rdm {
 
@@ -18,12 +19,7 @@ __global__ void k_dorn_fwd(const float* __restrict__ x, double* __restrict__ ord
   double* ob = ord + (long)b * K * HW + p;
   int count = 0;
   for (int k = 0; k < K; ++k) {
-    const float fa = fminf(fmaxf(xb[(long)(2 * k) * HW], 1e-8f), 1e4f);
-    const float fb = fminf(fmaxf(xb[(long)(2 * k + 1) * HW], 1e-8f), 1e4f);
-    const double a = (double)fa, bb = (double)fb;
-    const double m = fmax(a, bb);
-    const double ea = exp(a - m), eb = exp(bb - m);
-    const double P = eb / (ea + eb);
+    const double P = dorn_pair_prob(xb[(long)(2 * k) * HW], xb[(long)(2 * k + 1) * HW]);      // postproc_dev.h
     ob[(long)k * HW] = P;
     count += (P > 0.5) ? 1 : 0;
   }

@@ -5,69 +5,11 @@
 #include <algorithm>
 
 #include "rdm_common.h"
+#include "postproc_dev.h"
 
 namespace rdm {
 
-// ---------------------------------------------------------------------------------------------
-// Bicubic resize, BIT-EXACT with the float64 CPU path of the reference's `F.interpolate(mode='bicubic',
-// align_corners=False)` (computations.py:308-311; third party: torch 2.10 ATen, UpSampleKernel.cpp
-// `cpu_upsample_generic` + UpSample.h `get_cubic_upsample_coefficients` / `guard_index_and_lambda`).
-// The exact rounding sequence of that build (which mul+add pairs its compiler contracted into FMAs) was
-// pinned against the library itself (oracle/bicubic_aten.c restates it; tests/test_oracle_ops.py holds it
-// to the reference-generated fixtures with assert_array_equal, 3 318 further outputs were compared while
-// deriving it).  Every operation below is therefore explicit: contraction is OFF, fused steps are fma().
-//   real  = fma(scale, i + 0.5, -0.5), scale = in / out
-//   index = min((long)floorf((float)real), in - 1)           (float floor, as ATen writes it)
-//   t     = min(max(real - index, 0), 1)
-//   c2(x) = fma(fma(A, x, -5A), x, 8A) * x - 4A              (outer taps, x = t + 1 and (1 - t) + 1)
-//   c1(x) = fma(A + 2, x, -(A + 3)) * x * x + 1              (inner taps, x = t and 1 - t)
-//   dot4  = fma(v3, w3, fma(v2, w2, fma(v0, w0, v1 * w1)))   (rows along x first, then the 4 rows along y)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cubic_coeffs(double t, double (&c)[4]) {
-#pragma clang fp contract(off)
-  const double A = -0.75;
-  const double x2 = 1.0 - t;
-  const double xa = t + 1.0, xb = x2 + 1.0;
-  c[0] = __builtin_fma(__builtin_fma(A, xa, -5.0 * A), xa, 8.0 * A) * xa - 4.0 * A;
-  c[1] = __builtin_fma(A + 2.0, t, -(A + 3.0)) * t * t + 1.0;
-  c[2] = __builtin_fma(A + 2.0, x2, -(A + 3.0)) * x2 * x2 + 1.0;
-  c[3] = __builtin_fma(__builtin_fma(A, xb, -5.0 * A), xb, 8.0 * A) * xb - 4.0 * A;
-}
-
-__device__ __forceinline__ int cubic_index(int i, int n_in, int n_out, double& t) {
-#pragma clang fp contract(off)
-  const double scale = (double)n_in / (double)n_out;
-  const double real = __builtin_fma(scale, (double)i + 0.5, -0.5);
-  const long idx = min((long)floorf((float)real), (long)n_in - 1);
-  t = fmin(fmax(real - (double)idx, 0.0), 1.0);
-  return (int)idx;
-}
-
-__device__ __forceinline__ double dot4(const double (&v)[4], const double (&w)[4]) {
-#pragma clang fp contract(off)
-  double acc = v[1] * w[1];
-  acc = __builtin_fma(v[0], w[0], acc);
-  acc = __builtin_fma(v[2], w[2], acc);
-  return __builtin_fma(v[3], w[3], acc);
-}
-
-// align_corners=False, no antialias, border indices clamped
-__device__ __forceinline__ double bicubic_at(const double* __restrict__ src, int h, int w, int oh, int ow, int oy, int ox) {
-  double ty, tx, cy[4], cx[4], rows[4];
-  const int iy = cubic_index(oy, h, oh, ty), ix = cubic_index(ox, w, ow, tx);
-  cubic_coeffs(ty, cy);
-  cubic_coeffs(tx, cx);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int y = min(max(iy - 1 + i, 0), h - 1);
-    double v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = src[y * w + min(max(ix - 1 + j, 0), w - 1)];
-    rows[i] = dot4(v, cx);
-  }
-  return dot4(rows, cy);
-}
-
+// bicubic taps, the ordered workgroup sum and the pyramid layout: postproc_dev.h (shared with the fused predict tail, predict.hip)
 __global__ void k_resize_bicubic(const double* __restrict__ src, double* __restrict__ dst, int n, int h, int w, int oh, int ow) {
   const long total = (long)n * oh * ow;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -76,17 +18,6 @@ __global__ void k_resize_bicubic(const double* __restrict__ src, double* __restr
     const int oy = (int)(t % oh), b = (int)(t / oh);
     dst[i] = bicubic_at(src + (long)b * h * w, h, w, oh, ow, oy, ox);
   }
-}
-
-__device__ __forceinline__ double block_sum_bcast(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[wv] = v;
-  __syncthreads();
-  double r = 0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-  return r;
 }
 
 // one workgroup per sample: gm = exp(e * sum log x) (wavefront-reduced), dst = src / gm
@@ -102,8 +33,6 @@ __global__ __launch_bounds__(256) void k_gm_normalize(const double* __restrict__
     for (int i = threadIdx.x; i < n; i += 256) d[i] = s[i] / gm;
   }
 }
-
-__host__ __device__ __forceinline__ long level_off(int k) { return ((1L << (2 * k)) - 1) / 3; }
 
 // one workgroup per sample walks the pyramid top-down inside the packed output:
 // slot_k first holds d_k, then is divided in place by the nearest-upsampled d_{k-1}
@@ -134,7 +63,7 @@ __global__ void k_fine_detail_pred(const double* __restrict__ levels, const floa
     const long j = i % per;
     int k = 0;
     while (level_off(k + 1) <= j) ++k;
-    yhat[i] = (float)log(levels[i]) * w[k];
+    yhat[i] = fine_detail_value(levels[i], w[k]);
   }
 }
 

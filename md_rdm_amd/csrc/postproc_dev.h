@@ -1,0 +1,106 @@
+// Device arithmetic of the DORN head and the float64 post-processing, shared by the single-purpose kernels (dorn.hip, postproc.hip) and the
+// fused predict tail (predict.hip) so that both compute bit for bit the same values.  Device code only; not part of the C ABI.
+#pragma once
+#include "rdm_common.h"
+
+namespace rdm {
+
+// ---------------------------------------------------------------------------------------------
+// DORN pair (RDM_Net.py:313-345): clamp in f32, two-way softmax in f64, P = probability of the second logit
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float dorn_clamp(float x) { return fminf(fmaxf(x, 1e-8f), 1e4f); }
+
+__device__ __forceinline__ double dorn_pair_prob(float xa, float xb) {
+  const double a = (double)dorn_clamp(xa), bb = (double)dorn_clamp(xb);
+  const double m = fmax(a, bb);
+  const double ea = exp(a - m), eb = exp(bb - m);
+  return eb / (ea + eb);
+}
+
+// The decision `dorn_pair_prob(xa, xb) > 0.5` without the two f64 exponentials: it equals `clamp(xb) > clamp(xa)`, exactly.
+//   b > a:  eb = exp(0) = 1 and ea = exp(a - b) with b - a >= one f32 ulp at 1e-8 = 2^-50, so ea <= 1 - 8 * 2^-53 (the exponential is
+//           accurate to 1 ulp: at least 7 ulps below 1), 1 + ea < 2 after rounding and P = 1 / (1 + ea) rounds to a double above 0.5;
+//   b < a:  ea = 1, eb <= 1 - 7 * 2^-53 and eb / (1 + eb) <= 0.5 - 1.5 * 2^-52, eight representable doubles below 0.5;
+//   b == a: P = 1 / 2 exactly, not above 0.5.
+// tests/test_gpu_predict.py holds the two forms against each other on neighbouring floats across the whole clamp range.
+__device__ __forceinline__ bool dorn_pair_above_half(float xa, float xb) { return dorn_clamp(xb) > dorn_clamp(xa); }
+
+// ---------------------------------------------------------------------------------------------
+// Bicubic resize, BIT-EXACT with the float64 CPU path of the reference's `F.interpolate(mode='bicubic',
+// align_corners=False)` (computations.py:308-311; third party: torch 2.10 ATen, UpSampleKernel.cpp
+// `cpu_upsample_generic` + UpSample.h `get_cubic_upsample_coefficients` / `guard_index_and_lambda`).
+// The exact rounding sequence of that build (which mul+add pairs its compiler contracted into FMAs) was
+// pinned against the library itself (oracle/bicubic_aten.c restates it; tests/test_oracle_ops.py holds it
+// to the reference-generated fixtures with assert_array_equal, 3 318 further outputs were compared while
+// deriving it).  Every operation below is therefore explicit: contraction is OFF, fused steps are fma().
+//   real  = fma(scale, i + 0.5, -0.5), scale = in / out
+//   index = min((long)floorf((float)real), in - 1)           (float floor, as ATen writes it)
+//   t     = min(max(real - index, 0), 1)
+//   c2(x) = fma(fma(A, x, -5A), x, 8A) * x - 4A              (outer taps, x = t + 1 and (1 - t) + 1)
+//   c1(x) = fma(A + 2, x, -(A + 3)) * x * x + 1              (inner taps, x = t and 1 - t)
+//   dot4  = fma(v3, w3, fma(v2, w2, fma(v0, w0, v1 * w1)))   (rows along x first, then the 4 rows along y)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cubic_coeffs(double t, double (&c)[4]) {
+#pragma clang fp contract(off)
+  const double A = -0.75;
+  const double x2 = 1.0 - t;
+  const double xa = t + 1.0, xb = x2 + 1.0;
+  c[0] = __builtin_fma(__builtin_fma(A, xa, -5.0 * A), xa, 8.0 * A) * xa - 4.0 * A;
+  c[1] = __builtin_fma(A + 2.0, t, -(A + 3.0)) * t * t + 1.0;
+  c[2] = __builtin_fma(A + 2.0, x2, -(A + 3.0)) * x2 * x2 + 1.0;
+  c[3] = __builtin_fma(__builtin_fma(A, xb, -5.0 * A), xb, 8.0 * A) * xb - 4.0 * A;
+}
+
+__device__ __forceinline__ int cubic_index(int i, int n_in, int n_out, double& t) {
+#pragma clang fp contract(off)
+  const double scale = (double)n_in / (double)n_out;
+  const double real = __builtin_fma(scale, (double)i + 0.5, -0.5);
+  const long idx = min((long)floorf((float)real), (long)n_in - 1);
+  t = fmin(fmax(real - (double)idx, 0.0), 1.0);
+  return (int)idx;
+}
+
+__device__ __forceinline__ double dot4(const double (&v)[4], const double (&w)[4]) {
+#pragma clang fp contract(off)
+  double acc = v[1] * w[1];
+  acc = __builtin_fma(v[0], w[0], acc);
+  acc = __builtin_fma(v[2], w[2], acc);
+  return __builtin_fma(v[3], w[3], acc);
+}
+
+// align_corners=False, no antialias, border indices clamped
+__device__ __forceinline__ double bicubic_at(const double* __restrict__ src, int h, int w, int oh, int ow, int oy, int ox) {
+  double ty, tx, cy[4], cx[4], rows[4];
+  const int iy = cubic_index(oy, h, oh, ty), ix = cubic_index(ox, w, ow, tx);
+  cubic_coeffs(ty, cy);
+  cubic_coeffs(tx, cx);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int y = min(max(iy - 1 + i, 0), h - 1);
+    double v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = src[y * w + min(max(ix - 1 + j, 0), w - 1)];
+    rows[i] = dot4(v, cx);
+  }
+  return dot4(rows, cy);
+}
+
+// sum over the workgroup in a FIXED order (lanes by shuffle, then the wavefronts in sequence), broadcast to every thread
+__device__ __forceinline__ double block_sum_bcast(double v, double* sh) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+  __syncthreads();
+  if (l == 0) sh[wv] = v;
+  __syncthreads();
+  double r = 0;
+  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
+  return r;
+}
+
+// first element of level k in a packed pyramid [d_0 (1x1) | F_1 (2x2) | ...]
+__host__ __device__ __forceinline__ long level_off(int k) { return ((1L << (2 * k)) - 1) / 3; }
+
+// y_hat_k = float(log F_k) * w_k   (single-candidate make_pred: A^T.float() @ w.float())
+__device__ __forceinline__ float fine_detail_value(double level, float w) { return (float)log(level) * w; }
+
+}  // namespace rdm

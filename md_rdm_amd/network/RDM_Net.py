@@ -704,6 +704,52 @@ class DepthEstimationNet(BaseModel):
 
     segment_slices = stage_slices          # former name (4 coarse segments)
 
+    # ---- image -> depth map (no target): recombination(model(x)[0]), computations.py:394-421 on RDM_Net.py:70-135 --------
+    def _fused_tail_levels(self, oh, ow):
+        """log2 of the head side when rdm_predict_tail_f32 covers this model and head (ordinal-only, square power-of-two side <= 16, one
+        weight per level), else None."""
+        if self.relative_ids or oh != ow or oh & (oh - 1) or oh > 16:
+            return None
+        n = oh.bit_length() - 1
+        if any(self.weight_layer.get(k).numel() != 1 for k in range(n + 1)):
+            return None
+        return n
+
+    def predict(self, x, linear=False, size=None, return_counts=False):
+        """The (B,1,128,128) float64 map of log relative depth for a batch of images - what the reference computes for an image,
+        ``recombination(model(x)[0])`` (optimize_components returns its predictions unchanged, computations.py:499-510) - without a target.
+        Eval mode only; the forward runs at the model's ``precision``.  The ordinal-only model with a square power-of-two head (226/228-pixel
+        inputs) takes the d_1 logits to the map in ONE launch (rdm_predict_tail_f32); models with relative decoders and rectangular heads
+        compose the single operators exactly as ``forward`` + ``recombination`` do.
+        ``linear``: return float32 ``exp`` of the map instead.  ``size=(H, W)``: bicubic ``resize`` of the log map first.
+        ``return_counts``: also return the (B,1,h,w) int64 DORN count map (``forward``'s second result)."""
+        if self.training:
+            raise _lib.RdmError("predict is inference only (eval-mode BatchNorm): call model.eval() first")
+        if not x.is_cuda:
+            raise _lib.RdmError("DepthEstimationNet runs on the MI355X only (input is on %s); there is no CPU fallback" % x.device)
+        with torch.no_grad():
+            B, _, H, W = x.shape
+            _, _, oh, ow = self._plan(B, H, W)
+            n = self._fused_tail_levels(oh, ow)
+            lin = None
+            if n is not None:
+                logits = self._native_forward_bf16(x) if self.precision == "bf16" else self._native_forward(x)
+                wv = torch.cat([self.weight_layer.get(k).reshape(-1)[:1].float() for k in range(n + 1)]).contiguous()
+                out = torch.empty(B, 1, 128, 128, dtype=torch.float64, device=x.device)
+                counts = torch.empty(B, 1, oh, ow, dtype=torch.int64, device=x.device) if return_counts else None
+                if linear and size is None:
+                    lin = torch.empty(B, 1, 128, 128, dtype=torch.float32, device=x.device)
+                _lib.check(_lib.lib().rdm_predict_tail_f32(_lib.ptr(logits), _lib.ptr(wv), _lib.ptr(out), _lib.ptr(counts), _lib.ptr(lin), B, logits.shape[1] // 2,
+                                                           oh, ow, 7, 0, _lib.stream()))
+            else:
+                y_hat, counts, _ = self.forward(x)
+                out = cp.recombination(list(y_hat))
+            if size is not None:
+                out = cp.resize(out, tuple(size))
+            if linear:
+                out = lin if lin is not None else torch.exp(out).float()
+            return (out, counts) if return_counts else out
+
     # ---- the reference forward (RDM_Net.py:70-135) -----------------------------------------
     def forward(self, x):
         bf16 = self.precision == "bf16"

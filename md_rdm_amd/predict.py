@@ -1,0 +1,123 @@
+"""Image in, depth map out: ``DepthEstimationNet.predict`` from the command line.  The reference has no such command; what it computes for
+an image without a target is ``recombination(model(x)[0])`` (network/computations.py:394-421, :499-510), a 128x128 map of log relative depth.
+
+  python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps frame0.npy frame1.png
+  python -m md_rdm_amd.predict --synthetic 8 --precision 16 --batch_size 8 --out maps
+
+Inputs are uint8 HxWx3 frames: ``.npy`` files, ``.npz`` files (array ``rgb``, else the first array) and, where Pillow is installed,
+ordinary image files.  They pass through the GPU test transform of dataloaders/nyu.py (Resize(500) -> CenterCrop((480, 640)) ->
+Resize(--size)); at least 480x640 after the first resize, like the reference's test_preprocess.  ``--synthetic N`` feeds N hash-generated
+network inputs (filler.synthetic_batch) of --size instead.  One ``.npy`` per input lands in --out: the (1,128,128) float64 log map,
+float32 ``exp`` of it with --linear, resized to the frame region the network saw ((480, 640), or --size for synthetic inputs) with --full_res.
+"""
+import os
+import sys
+import time
+from argparse import ArgumentParser
+
+NO_GPU = "md_rdm_amd.predict: no GPU is visible to this process (torch.cuda.is_available() is False); the predict path runs on the MI355X only"
+
+
+def build_parser():
+    p = ArgumentParser("md_rdm_amd.predict", description="Depth maps (log relative depth, 128x128) for images, on the MI355X-native stack")
+    p.add_argument("inputs", nargs="*", help=".npy / .npz uint8 HxWx3 frames, or image files (needs Pillow)")
+    p.add_argument("--checkpoint", type=str, default=None, help="Lightning .ckpt or state_dict; without it the hash-filled model is used (a warning says so)")
+    p.add_argument("--precision", type=int, default=32, choices=[16, 32], help="32: float32 native plan; 16: bf16 MFMA inference path")
+    p.add_argument("--batch_size", type=int, default=8)
+    p.add_argument("--size", type=int, nargs=2, default=[226, 226], metavar=("H", "W"), help="network input size (module.py:19 feeds 226x226)")
+    p.add_argument("--out", type=str, required=True, help="directory for the .npy maps")
+    p.add_argument("--linear", action="store_true", help="write float32 exp(map) instead of the float64 log map")
+    p.add_argument("--full_res", action="store_true", help="bicubic resize of the log map to the frame region the network saw (480x640; --size for --synthetic)")
+    p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N hash-generated inputs (filler.synthetic_batch) instead of files")
+    p.add_argument("--relative_decoders", type=int, nargs="*", default=[], help="subset of 6 7 8 9 10, as in md_rdm_amd.train")
+    return p
+
+
+def load_frame(path):
+    """uint8 (H,W,3)"""
+    import numpy as np
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        a = np.load(path)
+    elif ext == ".npz":
+        with np.load(path) as z:
+            a = z["rgb"] if "rgb" in z.files else z[z.files[0]]
+    else:
+        try:
+            from PIL import Image
+        except ImportError:
+            raise SystemExit(f"md_rdm_amd.predict: {path}: reading image files needs Pillow, which is not installed; pass .npy / .npz uint8 HxWx3 frames instead")
+        with Image.open(path) as im:
+            a = np.asarray(im.convert("RGB"))
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+        raise SystemExit(f"md_rdm_amd.predict: {path}: need a uint8 HxWx3 frame, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if bool(args.synthetic) == bool(args.inputs):
+        raise SystemExit("md_rdm_amd.predict: give input files or --synthetic N (not both)")
+    if args.batch_size < 1:
+        raise SystemExit("md_rdm_amd.predict: --batch_size must be positive")
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit(NO_GPU)
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+
+    from . import checkpoint, filler
+    from .dataloaders import nyu
+    from .network.RDM_Net import DepthEstimationNet
+    model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
+    if args.checkpoint:
+        checkpoint.from_lightning(model, args.checkpoint)
+    else:
+        print("warning: no --checkpoint: using the deterministic hash-filled weights (filler.fill_state_dict) - the maps are not depth", flush=True)
+        filler.fill_state_dict(model.state_dict())
+    model = model.to(dev).eval().set_precision("bf16" if args.precision == 16 else "f32")
+    size = tuple(args.size)
+    os.makedirs(args.out, exist_ok=True)
+
+    # (name, source) in order; batches are runs of inputs that share the raw frame size
+    if args.synthetic:
+        xs = filler.synthetic_batch(args.synthetic, size[0], size[1])[0]
+        items = [("synthetic_%04d" % i, xs[i]) for i in range(args.synthetic)]
+    else:
+        items = [(os.path.splitext(os.path.basename(p))[0], load_frame(p)) for p in args.inputs]
+    pre = nyu.NyuGpuPreprocessor(resize=500, output_size=size, device=dev)
+    seen, i = {}, 0
+    while i < len(items):
+        j = i + 1
+        while j < len(items) and j - i < args.batch_size and items[j][1].shape == items[i][1].shape:
+            j += 1
+        batch = np.stack([a for _, a in items[i:j]])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if args.synthetic:
+            x = torch.from_numpy(batch).to(dev)
+            region = size
+        else:
+            rgb = torch.from_numpy(batch).to(dev)
+            H, W = batch.shape[1:3]
+            dummy = torch.zeros(len(batch), H, W, dtype=torch.float32, device=dev)        # the transform carries a depth plane; there is none here
+            try:
+                params = [nyu.test_params((H, W), size) for _ in range(len(batch))]
+            except ValueError as e:
+                raise SystemExit("md_rdm_amd.predict: %s (%dx%d frame): %s" % (items[i][0], H, W, e))
+            x, _ = pre(rgb, dummy, params)
+            region = (480, 640)
+        out = model.predict(x, linear=args.linear, size=region if args.full_res else None).cpu().numpy()
+        dt = time.perf_counter() - t0
+        for (name, _), m in zip(items[i:j], out):
+            k = seen.get(name, 0)
+            seen[name] = k + 1
+            np.save(os.path.join(args.out, name + ("" if k == 0 else "_%d" % k) + ".npy"), m)
+        print("batch of %d: %.1f images/s" % (j - i, (j - i) / dt), flush=True)
+        i = j
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
