@@ -562,6 +562,21 @@ int rdm_predict_tail_f32(const float* logits, const float* w, double* log_map, i
  *          sum |p-t|/t, sum (p-t)^2/t, sum sqrt((p-t)^2/t)]; the host divides by count (after an all-reduce under DP) */
 int rdm_depth_metrics_f64(const double* pred, const double* target, int64_t n, double* out10, rdm_stream_t stream);
 
+/* Batched evaluation, target and metric side in ONE launch (one workgroup per sample).  Per sample, in the order of the composed path:
+ * module.py:68 (bicubic resize of the raw depth to 128x128 in float64, the values of rdm_resize_bicubic_f64 bit for bit) + module.py:75-78
+ * (mask: a valid pixel becomes y + (double)(float)1e-4, a non-positive one - bicubic overshoot included - (double)(1.0f + 1e-4f):
+ * `(y <= 0) + 1e-4` is a float32 tensor in torch) + module.py:145-149 / computations.py:244-255 (geometric mean over the 16384 pixels,
+ * exponent 1/128^2, summed in rdm_gm_normalize_f64's order: bit-identical) + metrics.py:48-128 (the ten sums of rdm_depth_metrics_f64 of
+ * pred against target / gm).
+ *   pred (B,1,128,128) f64, the predicted map;  depth (B,1,h,w) float32, or float64 with depth_is_f64 != 0 (float32 is widened on load);
+ *   rows (B,10) f64, one row of sums per sample, written with plain stores: no atomics, no memset, bit-reproducible;
+ *   target_out (B,1,128,128) f64 normalised target, or NULL;  gm_out (B) f64 geometric means, or NULL.
+ * flags: RDM_EVAL_EXP_PRED compares exp(pred) instead of pred - a DEPARTURE from the reference, which compares the log-domain map as it is
+ * (module.py:117); 0 is the reference's behaviour. */
+#define RDM_EVAL_EXP_PRED 1
+int rdm_eval_target_metrics_f64(const double* pred, const void* depth, int32_t depth_is_f64, int32_t batch, int32_t h, int32_t w, double* rows,
+                                double* target_out, double* gm_out, int32_t flags, rdm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * NYU input pipeline: dataloaders/nyu_dataloader.py:240-272 training_preprocess and
  * :274-287 validation_preprocess for a whole batch on the GPU, bit-exact with the Pillow arithmetic the

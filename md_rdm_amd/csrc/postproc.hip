@@ -245,18 +245,7 @@ __global__ __launch_bounds__(256) void k_depth_metrics(const double* __restrict_
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const double t = target[i];
     if (!(t > 0)) continue;
-    const double p = fmax(pred[i], 1e-7);
-    const double r = fmax(p / t, t / p), d = p - t;
-    acc[0] += 1;
-    acc[1] += r < 1.25 ? 1 : 0;
-    acc[2] += r < 1.25 * 1.25 ? 1 : 0;
-    acc[3] += r < 1.25 * 1.25 * 1.25 ? 1 : 0;
-    acc[4] += d * d;
-    acc[5] += fabs(d);
-    acc[6] += fabs(log10(p) - log10(t));
-    acc[7] += fabs(d) / t;
-    acc[8] += d * d / t;
-    acc[9] += sqrt(d * d / t);
+    depth_metric_terms(pred[i], t, acc);                // postproc_dev.h (shared with the fused evaluation kernel, evalmetrics.hip)
   }
 #pragma unroll
   for (int k = 0; k < 10; ++k) {

@@ -1,5 +1,6 @@
 // Device arithmetic of the DORN head and the float64 post-processing, shared by the single-purpose kernels (dorn.hip, postproc.hip) and the
-// fused predict tail (predict.hip) so that both compute bit for bit the same values.  Device code only; not part of the C ABI.
+// fused kernels (predict.hip: the predict tail; evalmetrics.hip: the evaluation target + metrics) so that all compute bit for bit the same
+// values.  Device code only; not part of the C ABI.
 #pragma once
 #include "rdm_common.h"
 
@@ -68,8 +69,9 @@ __device__ __forceinline__ double dot4(const double (&v)[4], const double (&w)[4
   return __builtin_fma(v[3], w[3], acc);
 }
 
-// align_corners=False, no antialias, border indices clamped
-__device__ __forceinline__ double bicubic_at(const double* __restrict__ src, int h, int w, int oh, int ow, int oy, int ox) {
+// align_corners=False, no antialias, border indices clamped.  T = double, or float widened on load (exact): the arithmetic is float64 either way
+template <typename T>
+__device__ __forceinline__ double bicubic_at(const T* __restrict__ src, int h, int w, int oh, int ow, int oy, int ox) {
   double ty, tx, cy[4], cx[4], rows[4];
   const int iy = cubic_index(oy, h, oh, ty), ix = cubic_index(ox, w, ow, tx);
   cubic_coeffs(ty, cy);
@@ -79,7 +81,7 @@ __device__ __forceinline__ double bicubic_at(const double* __restrict__ src, int
     const int y = min(max(iy - 1 + i, 0), h - 1);
     double v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = src[y * w + min(max(ix - 1 + j, 0), w - 1)];
+    for (int j = 0; j < 4; ++j) v[j] = (double)src[y * w + min(max(ix - 1 + j, 0), w - 1)];
     rows[i] = dot4(v, cx);
   }
   return dot4(rows, cy);
@@ -95,6 +97,37 @@ __device__ __forceinline__ double block_sum_bcast(double v, double* sh) {
   double r = 0;
   for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
   return r;
+}
+
+// block_sum_bcast of the FIRST `waves` wavefronts of a larger workgroup (every thread calls it; the others' `v` is ignored): the same
+// order of additions as block_sum_bcast in a workgroup of `waves` wavefronts, so a wide kernel can restate a narrow kernel's sum bit for bit
+__device__ __forceinline__ double head_waves_sum_bcast(double v, double* sh, int waves) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+  __syncthreads();
+  if (l == 0 && wv < waves) sh[wv] = v;
+  __syncthreads();
+  double r = 0;
+  for (int i = 0; i < waves; ++i) r += sh[i];
+  return r;
+}
+
+// One pixel of the validation metrics (metrics.py:48-128): skipped unless target > 0, pred clamped to >= 1e-7; acc = the ten sums of
+// rdm_depth_metrics_f64 (include/rdm_hip.h)
+__device__ __forceinline__ void depth_metric_terms(double pred, double t, double (&acc)[10]) {
+  if (!(t > 0)) return;
+  const double p = fmax(pred, 1e-7);
+  const double r = fmax(p / t, t / p), d = p - t;
+  acc[0] += 1;
+  acc[1] += r < 1.25 ? 1 : 0;
+  acc[2] += r < 1.25 * 1.25 ? 1 : 0;
+  acc[3] += r < 1.25 * 1.25 * 1.25 ? 1 : 0;
+  acc[4] += d * d;
+  acc[5] += fabs(d);
+  acc[6] += fabs(log10(p) - log10(t));
+  acc[7] += fabs(d) / t;
+  acc[8] += d * d / t;
+  acc[9] += sqrt(d * d / t);
 }
 
 // first element of level k in a packed pyramid [d_0 (1x1) | F_1 (2x2) | ...]

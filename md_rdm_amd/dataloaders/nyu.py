@@ -190,9 +190,11 @@ class PrefetchLoader:
     """Iterate (x, y) training / validation batches: a reader thread fills pinned staging buffers one batch ahead, the
     H2D copies run on a dedicated copy stream, and the augmentation kernels run on the consumer's stream after an event wait."""
 
-    def __init__(self, dataset, batch_size, shuffle=None, seed=0, device="cuda", drop_last=True, rank=0, world=1, workers=0):
+    def __init__(self, dataset, batch_size, shuffle=None, seed=0, device="cuda", drop_last=True, rank=0, world=1, workers=0, indices=None):
         """``workers`` (the reference's ``--worker``, module.py:19-27 DataLoader(num_workers=...)): threads that decode the raw samples of a
-        batch in parallel (h5 / npz reads release the GIL); 0 = decode in the reader thread.  The augmentation itself runs on the GPU."""
+        batch in parallel (h5 / npz reads release the GIL); 0 = decode in the reader thread.  The augmentation itself runs on the GPU.
+        ``indices`` (evaluation): the samples to visit, in that order and never shuffled; rank r takes ``indices[r::world]`` and NO sample is
+        dropped to equalise the shards (there is no collective inside an evaluation pass).  None: the whole dataset in equal shards."""
         self.ds, self.bs, self.device = dataset, batch_size, torch.device(device)
         self.pool = None
         if workers and workers > 0:
@@ -203,12 +205,25 @@ class PrefetchLoader:
         self.rng = np.random.default_rng(seed + rank)
         self.order_rng = np.random.default_rng(seed)            # same permutation on every rank, disjoint shards
         self.rank, self.world, self.drop_last = rank, world, drop_last
+        self.indices = None if indices is None else np.asarray(list(indices), dtype=np.int64)
         self.pre = NyuGpuPreprocessor(500 if dataset.split == "test" else dataset.resize, dataset.output_size, device)
-        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.copy_stream = None                                  # created with the first batch: constructing a loader touches no device
 
     def __len__(self):
-        n = len(self.ds) // self.world
+        n = len(self.ds) // self.world if self.indices is None else len(self.indices[self.rank::self.world])
         return n // self.bs if self.drop_last else (n + self.bs - 1) // self.bs
+
+    def batch_indices(self):
+        """This rank's batches of dataset indices for one pass (a shuffling loader draws its next permutation)."""
+        if self.indices is not None:
+            order = self.indices[self.rank::self.world]
+        else:
+            order = self.order_rng.permutation(len(self.ds)) if self.shuffle else np.arange(len(self.ds))
+            order = order[:len(order) // self.world * self.world][self.rank::self.world]      # equal shards: collectives in the step stay matched
+        batches = [order[i:i + self.bs] for i in range(0, len(order), self.bs)]
+        if self.drop_last:
+            batches = [b for b in batches if len(b) == self.bs]
+        return batches
 
     def _read(self, idx):
         raws = list(self.pool.map(self.ds.get_raw, idx)) if self.pool is not None else [self.ds.get_raw(i) for i in idx]
@@ -227,11 +242,9 @@ class PrefetchLoader:
         return rgb, dep, params
 
     def __iter__(self):
-        order = self.order_rng.permutation(len(self.ds)) if self.shuffle else np.arange(len(self.ds))
-        order = order[:len(order) // self.world * self.world][self.rank::self.world]      # equal shards: collectives in the step stay matched
-        batches = [order[i:i + self.bs] for i in range(0, len(order), self.bs)]
-        if self.drop_last:
-            batches = [b for b in batches if len(b) == self.bs]
+        batches = self.batch_indices()
+        if self.copy_stream is None:
+            self.copy_stream = torch.cuda.Stream(device=self.device)
         q = queue.Queue(maxsize=2)
 
         def worker():

@@ -1,0 +1,137 @@
+"""What does this checkpoint score on the NYU val / test split?  ``harness.evaluate`` from the command line: every sample of the split goes
+through ``DepthEstimationNet.predict`` and ONE launch per batch takes the predicted map and the loader's raw depth to the per-sample metric
+sums (``rdm_eval_target_metrics_f64``: resize to 128x128, mask, geometric-mean normalisation and the sums of metrics.py:48-128).  The figures
+are the means over the samples of the per-sample values - what the reference's batch-1 validation with Lightning's epoch mean reports
+(module.py:99-117) - whatever --batch_size is.
+
+  python -m md_rdm_amd.evaluate --checkpoint last.ckpt --nyu_path /data/nyudepthv2 --split val --out results.json
+  python -m md_rdm_amd.evaluate --synthetic 16 --batch_size 8 --precision 16 --out results.json
+  python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m md_rdm_amd.evaluate --checkpoint last.ckpt --nyu_path DIR --out results.json
+
+``--split val`` reads the samples through validation_preprocess (Resize + CenterCrop), ``--split test`` through test_preprocess
+(dataloaders/nyu.py).  ``--synthetic N`` scores N hash-generated samples instead (``synthetic_samples``).  Under WORLD_SIZE > 1 rank r scores
+samples r, r + world, ... (no sample is dropped; the shards may differ in size) and the ranks all-reduce the per-metric sums and the sample
+count once at the end; rank 0 prints and writes the result.
+"""
+import json
+import os
+import sys
+from argparse import ArgumentParser
+
+# multi-process GPU work on this ROCm stack needs dmabuf IPC (see md_rdm_amd/train.py); must be set before the first HIP call
+os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+
+NO_GPU = "md_rdm_amd.evaluate: no GPU is visible to this process (torch.cuda.is_available() is False); evaluation runs on the MI355X only"
+DEFAULT_METRICS = ["delta1", "delta2", "delta3", "mse", "mae", "log10", "rmse"]            # train.py's --metrics default
+
+
+def build_parser():
+    p = ArgumentParser("md_rdm_amd.evaluate", description="Score a checkpoint on the NYU val / test split, on the MI355X-native stack")
+    p.add_argument("--checkpoint", type=str, default=None, help="Lightning .ckpt or state_dict; without it the hash-filled model is used (a warning says so)")
+    p.add_argument("--nyu_path", type=str, default=None, help="directory of raw NYU samples (.h5 / .npz), as for md_rdm_amd.train")
+    p.add_argument("--split", type=str, default="val", choices=["val", "test"])
+    p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N hash-generated samples instead of --nyu_path")
+    p.add_argument("--batch_size", type=int, default=8)
+    p.add_argument("--precision", type=int, default=32, choices=[16, 32], help="32: float32 native plan; 16: bf16 MFMA inference path")
+    p.add_argument("--size", type=int, nargs=2, default=[226, 226], metavar=("H", "W"), help="network input size (module.py:19 feeds 226x226)")
+    p.add_argument("--relative_decoders", type=int, nargs="*", default=[], help="subset of 6 7 8 9 10, as in md_rdm_amd.train")
+    p.add_argument("--metrics", default=list(DEFAULT_METRICS), nargs="+")
+    p.add_argument("--exp_pred", action="store_true", help="compare exp(map) with the target instead of the log-domain map: this DEPARTS from the reference, "
+                   "which compares the recombination as it is (module.py:117)")
+    p.add_argument("--out", type=str, default=None, help="write the result as JSON here")
+    p.add_argument("--worker", default=6, type=int, help="threads that decode raw samples (--nyu_path)")
+    return p
+
+
+def synthetic_samples(n, h, w):
+    """(x (n,3,h,w) f32, depth (n,1,h,w) f32) for --synthetic: n copies of the margin-searched evaluation input (filler.MARGIN_SEEDS: every
+    DORN decision on it holds under the float32 noise of a different batch size or run, at 226x226), each with its own hash-generated depth -
+    so the scores do not depend on how the samples are batched."""
+    import numpy as np
+    from . import filler
+    x = filler.synthetic_batch(1, h, w, seed=filler.MARGIN_SEEDS["eval226"])[0]
+    y = filler.synthetic_batch(n, h, w)[1]
+    return np.ascontiguousarray(np.broadcast_to(x, (n,) + x.shape[1:])), y
+
+
+def shard(indices, rank, world):
+    """rank r of `world` takes indices[r::world]: every sample exactly once, shards of unequal size allowed"""
+    return list(indices)[rank::world]
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if bool(args.synthetic) == bool(args.nyu_path):
+        raise SystemExit("md_rdm_amd.evaluate: give --nyu_path DIR or --synthetic N (not both)")
+    if args.batch_size < 1:
+        raise SystemExit("md_rdm_amd.evaluate: --batch_size must be positive")
+    if args.synthetic < 0:
+        raise SystemExit("md_rdm_amd.evaluate: --synthetic must be positive")
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit(NO_GPU)
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    dev = torch.device("cuda", local)
+    torch.cuda.set_device(dev)
+    import torch.distributed as dist
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl", device_id=dev)
+
+    from . import checkpoint, filler, harness
+    from .metrics import MetricComputation
+    from .network.RDM_Net import DepthEstimationNet
+    try:
+        computer = MetricComputation(args.metrics)
+    except KeyError as e:
+        raise SystemExit("md_rdm_amd.evaluate: %s" % e.args[0])
+    model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
+    if args.checkpoint:
+        checkpoint.from_lightning(model, args.checkpoint)
+    else:
+        if rank == 0:
+            print("warning: no --checkpoint: using the deterministic hash-filled weights (filler.fill_state_dict) - the scores mean nothing", flush=True)
+        filler.fill_state_dict(model.state_dict())
+    model = model.to(dev).eval().set_precision("bf16" if args.precision == 16 else "f32")
+    H, W = args.size
+
+    if args.synthetic:
+        xs, ys = synthetic_samples(args.synthetic, H, W)
+        mine = shard(range(args.synthetic), rank, world)
+
+        def batches():
+            for i in range(0, len(mine), args.batch_size):
+                idx = mine[i:i + args.batch_size]
+                yield torch.from_numpy(xs[idx]).to(dev), torch.from_numpy(ys[idx]).to(dev)
+        source = "synthetic"
+    else:
+        from .dataloaders import NYUDataset, PrefetchLoader
+        ds = NYUDataset(args.nyu_path, split=args.split, output_size=(H, W))
+        loader = PrefetchLoader(ds, args.batch_size, shuffle=False, device=dev, drop_last=False, rank=rank, world=world, workers=args.worker,
+                                indices=range(len(ds)))
+
+        def batches():
+            return iter(loader)
+        source = args.split
+    result = harness.evaluate(model, batches(), computer, exp_pred=args.exp_pred)
+    if world > 1:
+        dist.destroy_process_group()
+    if rank == 0:
+        for name in computer.names:
+            print("%s %.6f" % (name, result[name]), flush=True)
+        print("n %d" % result["n"], flush=True)
+        if args.out:
+            record = {"split": source, "n": result["n"], "batch_size": args.batch_size, "precision": args.precision, "size": [H, W], "exp_pred": bool(args.exp_pred),
+                      "relative_decoders": list(args.relative_decoders), "checkpoint": args.checkpoint, "world": world,
+                      "metrics": {name: result[name] for name in computer.names}}
+            d = os.path.dirname(os.path.abspath(args.out))
+            os.makedirs(d, exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(record, fh, indent=1)
+                fh.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

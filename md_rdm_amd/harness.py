@@ -69,6 +69,42 @@ def validation_step(model, x, y):
     return y_hat, normalize(y)
 
 
+def evaluate(model, batches, metrics, exp_pred=False, return_maps=False):
+    """Score a model on an iterable of (x, raw depth) batches of ANY batch size: per batch ``model.predict(x)`` and ONE launch from the map and
+    the raw depth to a row of metric sums per sample (``MetricComputation.compute_rows``); the rows stay on the device and come over in one
+    copy after the last batch.  The result, {metric: mean over the samples of the per-sample value, "n": samples}, is what the reference's
+    batch-1 validation with Lightning's epoch mean reports (module.py:99-117; ``validation_step`` + ``MetricLogger.log_val`` here), whatever
+    the batch size: ``validation_step``'s prediction does not depend on the target (optimize_components returns its predictions unchanged),
+    so it is ``predict``'s map.  ``metrics``: a MetricComputation or a list of metric names.  Under an initialised process group every rank
+    passes its own shard (unequal shards are fine) and one all-reduce of the per-metric sums and the count makes the result global.
+    ``exp_pred``: compare exp(map) - not what the reference does.  ``return_maps``: also return the (n,1,128,128) maps of this rank."""
+    import torch.distributed as dist
+    from .metrics import MetricComputation, mean_over_shards
+    mc = metrics if isinstance(metrics, MetricComputation) else MetricComputation(list(metrics))
+    rows, maps = [], []
+    for x, y in batches:
+        pred = model.predict(x)
+        rows.append(mc.compute_rows(pred, y, exp_pred=exp_pred))
+        if return_maps:
+            maps.append(pred)
+    values = mc.values_from_rows(torch.cat(rows).cpu()) if rows else []          # the one device-to-host copy
+    sums = [0.0] * len(mc.names)
+    for v in values:                                                             # per-sample values summed in order, as MetricComputation.compute does
+        for i, s in enumerate(v):
+            sums[i] += s
+    n = len(values)
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        t = torch.tensor(sums + [float(n)], dtype=torch.float64, device=next(model.parameters()).device)
+        dist.all_reduce(t)
+        t = t.cpu()
+        sums, n = [float(s) for s in t[:-1]], int(t[-1])
+    if n == 0:
+        raise ValueError("evaluate: no samples")
+    means, n = mean_over_shards([(sums, n)])
+    result = dict(zip(mc.names, means), n=n)
+    return (result, torch.cat(maps)) if return_maps else result
+
+
 class FusedAdamW:
     """torch.optim.AdamW(lr) semantics (module.py:41) as one launch per contiguous TRAINABLE range of the model's flat parameter /
     gradient buffers (2 for the reference's live graph) + a tiny torch step for the 4 Weights scalars."""
