@@ -486,6 +486,33 @@ int rdm_net_backward_stage(rdm_net* net, const float* dlogits_nchw, void* const*
 /* test/debug access to the workspace layout: byte offset + float count of a named internal buffer
  * ("blk0".."blk3" block activations NHWC, "G0".."G3" their gradients, "logits", "Y<b>_<i>" bottlenecks ...) */
 int rdm_net_buffer(const rdm_net* net, const char* name, int64_t* offset_bytes, int64_t* numel);
+/* test/debug access to the plan's kernel routing: the plan decides ONCE per (geometry, options) which kernel family runs each GEMM of a dense layer
+ * (_DenseLayer: norm1-relu-conv1 1x1, norm2-relu-conv2 3x3; blocks 0..2 = encoder.dense_e2..e4, RDM_Net.py:73-94; 3 = d_1.dense_layer, :137-159)
+ * and which operand encoding each producer writes for its consumers.  `flags` receives the rdm_net_route_flags of layer `layer` of dense block
+ * `block`; the encodings depend on whether the layer's conv1.weight has a gradient slot (`conv1_has_grad`; freeze_encoder, RDM_Net.py:65-67).
+ * Needs no device.  An rdm_net_set_option other than RDM_NET_OPT_JOIN_PER_SEGMENT re-resolves the table. */
+typedef enum rdm_net_route_flags {
+  /* per block, forward */
+  RDM_ROUTE_PIPELINED = 1 << 0,   /* few-pixel block: conv1 of layer i+1 runs one layer ahead on the side stream */
+  RDM_ROUTE_RAW = 1 << 1,         /* ... and, in training, the consuming convs form the BatchNorm affine from the channel sums themselves */
+  RDM_ROUTE_WINO_FWD = 1 << 2,    /* conv2 forward as Winograd F(2x2, 3x3) */
+  RDM_ROUTE_WINO_X6 = 1 << 3,     /* ... on the bf16x6 kernel */
+  RDM_ROUTE_XF = 1 << 4,          /* conv1 forward on the three-way-split bf16x6 kernel */
+  RDM_ROUTE_DEFER = 1 << 5,       /* deferred norm1 backward (RDM_NET_OPT_DEFER_NORM1) */
+  /* per layer, backward: set = the split kernels (XS), clear = the f32 MFMA kernels */
+  RDM_ROUTE_WG3_XS = 1 << 6,      /* 3x3 weight gradient: XS, ... */
+  RDM_ROUTE_WG3_WINO = 1 << 7,    /* ... Winograd F(3x3, 2x2), or (neither bit) the direct kernel */
+  RDM_ROUTE_DG3_XS = 1 << 8,      /* 3x3 input gradient */
+  RDM_ROUTE_DG1_XS = 1 << 9,      /* 1x1 input gradient */
+  RDM_ROUTE_WG1_XS = 1 << 10,     /* 1x1 weight gradient */
+  RDM_ROUTE_NP1 = 1 << 11,        /* one bf16 MFMA per product on the XS routes (RDM_NET_OPT_GEMM_BF16); clear = three */
+  /* operand encodings */
+  RDM_ROUTE_G_FRAME = 1 << 12,    /* the 3x3 weight gradient reads the 48-channel gradient as a frame image of split rows */
+  RDM_ROUTE_DZ_BF16 = 1 << 13,    /* the bottleneck gradient dZ -> dY lives as bf16 rows */
+  RDM_ROUTE_DY_SPLIT = 1 << 14,   /* dY leaves the norm2 backward as split rows */
+  RDM_ROUTE_XH_SPLIT = 1 << 15    /* relu1(norm1(x)) reaches the 1x1 weight gradient as split rows */
+} rdm_net_route_flags;
+int rdm_net_route(const rdm_net* net, int32_t block, int32_t layer, int32_t conv1_has_grad, int32_t* flags);
 /* forward conv FLOPs (2*MAC) of one forward pass at this geometry, for roofline accounting */
 double rdm_net_forward_flops(const rdm_net* net);
 double rdm_net_backward_flops(const rdm_net* net);

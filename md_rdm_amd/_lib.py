@@ -113,6 +113,7 @@ _SIGNATURES = {
     "rdm_net_backward_stage_range": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32)]),
     "rdm_net_backward_stage": (C.c_int, [vp, vp, C.POINTER(vp), C.POINTER(vp), vp, sz, i32, vp]),
     "rdm_net_buffer": (C.c_int, [vp, C.c_char_p, C.POINTER(i64), C.POINTER(i64)]),
+    "rdm_net_route": (C.c_int, [vp, i32, i32, i32, C.POINTER(i32)]),
     "rdm_net_forward_flops": (f64, [vp]),
     "rdm_net_backward_flops": (f64, [vp]),
     "rdm_dorn_fwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
@@ -147,6 +148,11 @@ _SIGNATURES = {
     "rdm_page_reconstruct_f32": (C.c_int, [vp, vp, i32, i32, i32, vp]),
     "rdm_adamw_fused": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
 }
+
+# rdm_net_option (include/rdm_hip.h), for rdm_net_set_option
+NET_OPT_PACKED_3X3, NET_OPT_GRADS_PREZEROED, NET_OPT_DIRECT_3X3, NET_OPT_DETERMINISTIC, NET_OPT_JOIN_PER_SEGMENT = 1, 2, 3, 4, 5
+NET_OPT_SPLIT_BWD, NET_OPT_SPLIT_FWD, NET_OPT_GEMM_BF16, NET_OPT_DEFER_NORM1, NET_OPT_PREPACK = 6, 7, 8, 9, 10
+NET_OPT_SPLIT_ROWS, NET_OPT_WINO_X6, NET_OPT_FUSE_STATS3 = 11, 12, 13
 
 # librdm_bench.so (include/rdm_bench.h): measurement kernels of tools/ and bench_ops.py - not part of the product
 _BENCH_SIGNATURES = {

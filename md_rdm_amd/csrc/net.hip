@@ -136,6 +136,26 @@ struct Bump {
 struct LayerWs { size_t Y, statY, bn1, bn2, w2p, bs2, bs1, dw3; };   // bs*: backward [sum dz | sum dz*x] f64 slots      // bn*: [scale|shift|mean|rstd] x C floats
 struct BlockGeom { int H, W, M, ctot, cb; };
 
+// Kernel routing of the dense blocks: which kernel family runs each GEMM of the step and which operand encoding each producer writes for its
+// consumers.  A pure function of the geometry and the options (NetImpl::opt_*, *_min_pixels), filled by resolve_routes() - the one place that asks
+// the xs_*_supported predicates and compares pixel thresholds; forward_block / conv1_range / backward_block only read it.
+enum class Wg3 : unsigned char { DIRECT, WINO, XS };
+struct Encodings { bool g_frame, dz_bf16, dy_split, xh_split; };   // frame image of the 48-channel gradient (3x3 wgrad) / dZ -> dY lives as bf16 rows / dY leaves the norm2 backward as split rows / relu1(norm1(x)) is split once for the 1x1 wgrad
+struct LayerRoute {
+  Wg3 wg3;                        // 3x3 weight gradient: xsplit.hip, Winograd F(3x3, 2x2) or the direct f32 tap kernel
+  bool dg3_xs, dg1_xs, wg1_xs;    // 3x3 / 1x1 input gradient, 1x1 weight gradient: xsplit.hip (else the f32 MFMA kernels of igemm.hip)
+  int np;                         // bf16 MFMAs per product on the xsplit.hip gradient kernels: 3 (float32-equivalent) or 1 (RDM_NET_OPT_GEMM_BF16)
+  Encodings enc[2];               // [conv1.weight has a gradient slot]: without one the 1x1 weight gradient does not run and consumes nothing
+};
+struct BlockRoute {
+  bool pipelined, raw;            // forward of the few-pixel blocks: conv1 part A one layer ahead on the side stream / (training) the BatchNorm finalisations off the chain
+  bool wino, wino_x6;             // 3x3 forward as Winograd F(2x2, 3x3) / on the bf16x6 kernel
+  bool xf;                        // conv1 forward on launch_xs_fwd1x1
+  bool xs;                        // over the pixel threshold of the split gradient kernels (their weight images are pre-packed)
+  bool defer;                     // deferred norm1 backward: every layer's 1x1 input gradient runs on xsplit.hip (a layer that did not take it would neither consume nor forward the running (b, c) sums)
+  std::vector<LayerRoute> layer;
+};
+
 }  // namespace
 
 // The weight-gradient stream is ONE per device for the whole process, shared by every plan: the runtime maps streams onto a handful of hardware
@@ -159,7 +179,7 @@ static hipStream_t shared_side_stream(bool default_priority) {
   return s;
 }
 
-// pixel counts from which layout() sizes the per-layer pack buffers of the split kernels; xs_block() / xf_block() can never select below them
+// pixel counts from which layout() sizes the per-layer pack buffers of the split kernels; resolve_routes() can never select below them
 constexpr int XS_LAYOUT_MIN_PIXELS = 1024, XF_LAYOUT_MIN_PIXELS = 8192;
 
 struct NetImpl {
@@ -202,7 +222,6 @@ struct NetImpl {
   bool wino_fwd[4] = {false, false, false, false}, wino_wg[4] = {false, false, false, false};
   int wino_split[4] = {1, 1, 1, 1}, wino_split_x6[4] = {1, 1, 1, 1};
   int opt_wino_x6 = 0;         // RDM_NET_OPT_WINO_X6: the Winograd forward of those blocks on the bf16x6 kernel (float32-equivalent, bf16 matrix pipe)
-  bool wino_x6(int b) const { return opt_wino_x6 && opt_split_fwd && !opt_det && wino_fwd[b]; }
   size_t winoPartial = 0, winoPartialFloats = 0;
   size_t winoVy = 0, winoVyFloats = 0, winoQ = 0, winoQFloats = 0;     // weight-gradient scratch (side stream: one launch at a time)
   size_t xsW = 0, xsWBytes = 0, xfW = 0, xfWBytes = 0;
@@ -227,19 +246,20 @@ struct NetImpl {
   // the decoder (1 280 pixels) lost overall while every layer paid two weight-pack launches and the norm1 pass on its chain (53.3 vs 52.6 ms per step);
   // with RDM_NET_OPT_PREPACK and RDM_NET_OPT_DEFER_NORM1 it gains (49.8-50.1 vs 50.4-50.7): the threshold is the kernels' own minimum
   int xs_min_pixels = XS_LAYOUT_MIN_PIXELS;
-  bool xs_block(int b) const { return opt_split_bwd && !opt_det && bg[b].M >= xs_min_pixels; }
   int opt_split_rows = 1;      // RDM_NET_OPT_SPLIT_ROWS: dY and relu1(norm1(x)) reach the split 1x1 gradient kernels as SPLIT ROWS (xsplit_dev.h) written once by their producers
   size_t xsGf = 0;             // frame image of the layer's 48-channel output gradient for the split 3x3 weight gradient (side stream: one at a time)
   size_t xsXh = 0;             // split rows of the activation operand of the layer whose 1x1 weight gradient is running (side stream: one at a time)
   int opt_defer_norm1 = 1;     // RDM_NET_OPT_DEFER_NORM1: see k_bn_bwd_defer (elementwise.hip); blocks on the xs 1x1 dgrad only
   int opt_gemm_bf16 = 0;       // RDM_NET_OPT_GEMM_BF16: the launches routed to xsplit.hip round their operands to bf16 (one MFMA per product) - mixed-precision arithmetic
-  int xs_np() const { return (opt_gemm_bf16 & 2) ? 1 : 3; }      // value bits: 1 = the forward GEMMs, 2 = the gradient GEMMs (3 = both)
+                               // value bits: 1 = the forward GEMMs, 2 = the gradient GEMMs (3 = both)
   int opt_fuse_stats3 = 1;     // RDM_NET_OPT_FUSE_STATS3: the K-split 3x3 conv of the few-pixel blocks takes the channel statistics of its output in the same launch
   int opt_split_fwd = 0;       // RDM_NET_OPT_SPLIT_FWD: conv1 of the many-pixel blocks on the three-way-split bf16x6 forward kernel
   int xf_min_pixels = XF_LAYOUT_MIN_PIXELS;
-  bool xf_block(int b) const { return opt_split_fwd && !opt_det && bg[b].M >= xf_min_pixels; }
   int xs_wg3_min_pixels = 8192;
-  bool xs_block_wgrad3(int b) const { return xs_block(b) && bg[b].M >= xs_wg3_min_pixels; }
+  // the routing table: options arrive after plan(), so route() resolves it on first use and again after rdm_net_set_option
+  BlockRoute routes[4];
+  bool routes_valid = false;
+  int routes_variant = 0;      // development builds: the rdm_debug_variant value the table was resolved under
   // ---- reduced-precision forward (bf16.hip): prepared-weight buffer layout + activation workspace layout ----
   struct Bf16Layer { size_t w1, w3, bn1, bn2; };
   std::vector<Bf16Layer> bfl[4];
@@ -449,6 +469,64 @@ inline bool fuse_stats(int M, int N) {
   return (long)cdiv(M, 256) * cdiv(N, 48) >= 1536;   // flat between 512 and 3072 (swept)
 }
 
+void resolve_routes(NetImpl& n) {
+  const int np = (n.opt_gemm_bf16 & 2) ? 1 : 3;
+  const bool rows = n.opt_split_rows && np == 3;               // split rows / the frame image are operands of the three-product form
+  for (int b = 0; b < 4; ++b) {
+    const BlockGeom& g = n.bg[b];
+    const int layers = kBlocks[b].layers;
+    BlockRoute& R = n.routes[b];
+    // part A / part B of a pipelined conv1 add atomically: not in deterministic mode
+    R.pipelined = !fuse_stats(g.M, g.cb) && layers > 1 && g_variant != 8 && !n.opt_det;
+    R.wino = n.wino_fwd[b] && !n.opt_no_wino;
+    R.wino_x6 = R.wino && n.opt_wino_x6 && n.opt_split_fwd && !n.opt_det;
+    R.raw = R.pipelined && g.cb <= RAWBN_MAX_C && !R.wino && g.M <= 8192 && 2 * (g.W + 1) <= 128;
+    R.xf = n.opt_split_fwd && !n.opt_det && g.M >= n.xf_min_pixels;
+    R.xs = n.opt_split_bwd && !n.opt_det && g.M >= n.xs_min_pixels;
+    R.defer = R.xs && n.opt_defer_norm1;
+    WgradArgs w3{};
+    w3.g = geom3x3(n.B, g.H, g.W, 1); w3.N = GROWTH; w3.C = g.cb;
+    FwdArgs d3{};
+    d3.g = geom3x3(n.B, g.H, g.W, -1); d3.C = GROWTH; d3.N = g.cb; d3.M = g.M;
+    const Wg3 wg3 = R.xs && g.M >= n.xs_wg3_min_pixels && xs_wgrad3x3_supported(w3) ? Wg3::XS : n.wino_wg[b] && !n.opt_no_wino ? Wg3::WINO : Wg3::DIRECT;
+    const bool dg3_xs = R.xs && xs_dgrad3x3_supported(d3);
+    R.layer.assign(layers, LayerRoute{});
+    for (int i = 0; i < layers; ++i) {
+      const int cin = kBlocks[b].cin + i * GROWTH;
+      FwdArgs f1{}, d1{};
+      f1.g = d1.g = geom1x1(n.B, g.H, g.W); f1.M = d1.M = g.M;
+      f1.C = cin; f1.N = g.cb;                                 // conv1 forward over all of the layer's input channels
+      d1.C = g.cb; d1.N = cin;                                 // its input gradient
+      WgradArgs w1{};
+      w1.g = f1.g; w1.N = g.cb; w1.C = cin;
+      LayerRoute& r = R.layer[i];
+      r.np = np; r.wg3 = wg3; r.dg3_xs = dg3_xs;
+      r.dg1_xs = R.xs && xs_dgrad1x1_supported(d1);
+      r.wg1_xs = R.xs && xs_wgrad1x1_supported(w1);
+      R.xf = R.xf && xs_fwd1x1_supported(f1);
+      R.defer = R.defer && r.dg1_xs;
+      for (int has_grad = 0; has_grad < 2; ++has_grad) {
+        Encodings& e = r.enc[has_grad];
+        e.g_frame = rows && wg3 == Wg3::XS;
+        // mixed-precision arithmetic (RDM_NET_OPT_GEMM_BF16): when all three consumers / producers of the layer's dZ -> dY tensor are the
+        // one-product kernels, it LIVES as bf16 (they round it to bf16 at staging anyway): its four passes move half the bytes
+        e.dz_bf16 = has_grad && np == 1 && dg3_xs && r.dg1_xs && r.wg1_xs;
+        // float32 mode (RDM_NET_OPT_SPLIT_ROWS): dY leaves the norm2 backward as SPLIT ROWS when every consumer is a split kernel - they stage
+        // it verbatim instead of each converting and splitting every element; relu1(norm1(x)) likewise for the 1x1 weight gradient
+        e.dy_split = rows && r.dg1_xs && (!has_grad || r.wg1_xs);
+        e.xh_split = has_grad && rows && r.wg1_xs;
+      }
+    }
+  }
+  n.routes_valid = true;
+  n.routes_variant = g_variant;
+}
+
+const BlockRoute& route(NetImpl& n, int b) {
+  if (!n.routes_valid || n.routes_variant != g_variant) resolve_routes(n);
+  return n.routes[b];
+}
+
 // norm1 finalisation of layer i restricted to channels [c_lo, c_hi) of the block buffer
 int finalize_norm1(NetImpl& n, int b, int i, int c_lo, int c_hi, bool count_batch, void* ws, void* const* T, int training, hipStream_t s) {
   const BlockGeom& g = n.bg[b];
@@ -483,7 +561,7 @@ int conv1_range(NetImpl& n, int b, int i, int c_lo, int c_hi, bool accumulate, b
     a.a_scale = nullptr; a.a_shift = nullptr;
     a.a_sum = bst + c_lo; a.a_sq = bst + g.ctot + c_lo; a.a_gamma = F(T, L.bn1.w) + c_lo; a.a_beta = F(T, L.bn1.b) + c_lo; a.a_count = (double)g.M;
   }
-  if (n.xf_block(b) && !accumulate && !add_out && !raw_bn && xs_fwd1x1_supported(a)) {
+  if (route(n, b).xf && !accumulate && !add_out && !raw_bn) {
     const bool pk = n.pk_fwd_valid && !n.xfP[b].empty() && c_lo == 0 && c_hi == cin;
     return launch_xs_fwd1x1(a, fuse ? EPI_STORE_STATS : EPI_STORE, at<unsigned char>(ws, pk ? n.xfP[b][i] : n.xfW), pk ? xs_fwd1x1_workspace_bytes(cin, g.cb) : n.xfWBytes, s,
                             (n.opt_gemm_bf16 & 1) ? 1 : 6, pk);
@@ -502,7 +580,8 @@ int forward_block(NetImpl& n, int b, void* ws, void* const* T, int training, hip
   // everything except the newest 48 is already final while layer i is still running - so that bulk
   // ("part A") runs one layer ahead on the side stream, and only the 48-channel remainder ("part B",
   // 3 K-slabs) stays on the critical path.  Both parts add atomically into a zeroed Y.
-  const bool pipelined = !fuse_stats(g.M, g.cb) && layers > 1 && g_variant != 8 && !n.opt_det;   // part A / part B add atomically: not in deterministic mode
+  const BlockRoute& R = route(n, b);
+  const bool pipelined = R.pipelined;
   hipStream_t side = n.side;
   int rc;
   if (b == 0 && n.pk_fwd_valid) RDM_HIP_OK(hipStreamWaitEvent(s, n.ev_pkf, 0));                 // the packed conv1 weights of the split forward kernel
@@ -510,7 +589,7 @@ int forward_block(NetImpl& n, int b, void* ws, void* const* T, int training, hip
   // forms (scale, shift) from the channel sums itself (RAW prologue), the running statistics and the coefficients backward needs are written
   // by BATCHED finalisation launches (24 BatchNorms each) - and the 48-channel output slices of ALL layers are zeroed by ONE launch at the start
   // of the block (their K-split 3x3 convs then only add).  Per layer: 6 -> 3 launches on the chain, ~2.9 launches fewer in all.
-  const bool raw = pipelined && training && !n.opt_det && g.cb <= RAWBN_MAX_C && !(n.wino_fwd[b] && !n.opt_no_wino) && g.M <= 8192 && 2 * (g.W + 1) <= 128;
+  const bool raw = R.raw && training;
   if (raw && (rc = launch_zero_rows(blk + kBlocks[b].cin, g.M, g.ctot - kBlocks[b].cin, g.ctot, s))) return rc;
   // RAW mode bookkeeping (running statistics + the coefficients backward reads): nothing in forward waits for it, so it is BATCHED - up to
   // BN_BATCH BatchNorms per launch, enqueued on the caller's stream once their sums are final (the sums stay untouched until the next forward)
@@ -583,12 +662,12 @@ int forward_block(NetImpl& n, int b, void* ws, void* const* T, int training, hip
       c.accumulate = 1;                                                 // the slice was zeroed with the whole block at its start
       if (n.opt_fuse_stats3 && cdiv(g.M, 128) <= 128) c.tickets = at<unsigned>(ws, n.tickets);      // the last K split of a pixel tile takes the tile's statistics
     }
-    if (n.wino_fwd[b] && !n.opt_no_wino) {
+    if (R.wino) {
       // Winograd F(2x2, 3x3): the ordered reduction of the split partials also takes the channel statistics (no zero fill, no separate pass)
       WinoConv wv{};
       wv.A = Y; wv.lda = g.cb; wv.C = g.cb; wv.a_scale = bn2; wv.a_shift = bn2 + g.cb; wv.U = at<float>(ws, n.winoU[b][i]);
       wv.out = blk + cin; wv.ldc = g.ctot; wv.N = GROWTH; wv.B = n.B; wv.H = g.H; wv.W = g.W;
-      wv.x6 = n.wino_x6(b);
+      wv.x6 = R.wino_x6;
       wv.split = wv.x6 ? n.wino_split_x6[b] : n.wino_split[b]; wv.partial = at<float>(ws, n.winoPartial); wv.partial_floats = n.winoPartialFloats;
       if (training) { wv.stat0 = bst + cin; wv.stat1 = bst + g.ctot + cin; }
       if ((rc = launch_conv3x3_wino_fwd(wv, s))) return rc;
@@ -642,19 +721,6 @@ int zero_f32(float* p, size_t n, hipStream_t s) {
   return 0;
 }
 
-// every layer of block b can run the split 1x1 input gradient (whose epilogue carries the deferred norm1 backward)?
-static bool block_defers_norm1(const NetImpl& n, int b) {
-  if (!n.xs_block(b)) return false;
-  const BlockGeom& g = n.bg[b];
-  for (int i = 0; i < kBlocks[b].layers; ++i) {
-    FwdArgs e{};
-    e.g = geom1x1(n.B, g.H, g.W);
-    e.C = g.cb; e.N = kBlocks[b].cin + i * GROWTH; e.M = g.M;
-    if (!xs_dgrad1x1_supported(e)) return false;
-  }
-  return true;
-}
-
 int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, void* const* T, void* const* Gr, hipStream_t s) {
   const BlockGeom& g = n.bg[b];
   const int training = n.training_saved;
@@ -664,9 +730,12 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
   int rc;
   if ((rc = n.ensure_side())) return rc;
   hipStream_t side = n.side;
+  const BlockRoute& R = route(n, b);
   for (int i = i_hi; i >= i_lo; --i) {
     const LayerIdx& L = reg().layers[b][i];
     const LayerWs& W = n.lws[b][i];
+    const LayerRoute& r = R.layer[i];
+    const Encodings& enc = r.enc[Gr[L.conv1] != nullptr];
     const int cin = kBlocks[b].cin + i * GROWTH, cb = g.cb;
     const int par = i & 1;
     float* dZ = at<float>(ws, n.dZ[par]);
@@ -682,22 +751,23 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
       // packed gradients go straight to the caller's tensor; otherwise into a scratch that is unpacked to OIHW afterwards
       float* dW3 = n.opt_packed3x3 ? F(Gr, L.conv2) : at<float>(ws, W.dw3);
       RDM_HIP_OK(hipStreamWaitEvent(side, n.ev_go, 0));
-      WgradArgs xw{};
-      xw.g = geom3x3(n.B, g.H, g.W, 1);
-      xw.G = go; xw.ldg = g.ctot; xw.N = GROWTH; xw.Xs = Y; xw.ldx = cb; xw.C = cb; xw.x_scale = bn2; xw.x_shift = bn2 + cb;
-      xw.dW = dW3; xw.wtap = (long)GROWTH * cb; xw.ldw = cb; xw.xsplit = n.xs_np();
-      if (n.xs_block_wgrad3(b) && xs_wgrad3x3_supported(xw)) {
-        // split-precision direct kernel: accumulates with f32 atomics into the zeroed gradient
-        if (!(n.opt_packed3x3 && n.opt_prezeroed) && (rc = zero_f32(dW3, 9 * (size_t)GROWTH * cb, side))) return rc;
-        if (n.opt_split_rows && n.xs_np() == 3) {
+      WgradArgs w{};
+      w.g = geom3x3(n.B, g.H, g.W, 1);
+      w.G = go; w.ldg = g.ctot; w.N = GROWTH; w.Xs = Y; w.ldx = cb; w.C = cb; w.x_scale = bn2; w.x_shift = bn2 + cb;
+      w.dW = dW3; w.wtap = (long)GROWTH * cb; w.ldw = cb;
+      // the split-precision and the direct kernel accumulate with f32 atomics into the zeroed gradient
+      if (r.wg3 != Wg3::WINO && !(n.opt_packed3x3 && n.opt_prezeroed) && (rc = zero_f32(dW3, 9 * (size_t)GROWTH * cb, side))) return rc;
+      if (r.wg3 == Wg3::XS) {
+        w.xsplit = r.np;
+        if (enc.g_frame) {
           // the 48-channel gradient as a frame image of split rows, written once: the kernel's 43 column blocks x K splits then stage their
           // gradient slabs verbatim instead of each deriving every row's pixel and splitting it
           void* gf = at<unsigned char>(ws, n.xsGf);
           if ((rc = launch_frame_split_rows(go, g.ctot, GROWTH, n.B, g.H, g.W, gf, side))) return rc;
-          xw.G = static_cast<const float*>(gf); xw.ldg = 48; xw.g_frame = 1;
+          w.G = static_cast<const float*>(gf); w.ldg = 48; w.g_frame = 1;
         }
-        if ((rc = launch_xs_wgrad3x3(xw, side))) return rc;
-      } else if (n.wino_wg[b] && !n.opt_no_wino) {
+        if ((rc = launch_xs_wgrad3x3(w, side))) return rc;
+      } else if (r.wg3 == Wg3::WINO) {
         // Winograd F(3x3, 2x2): writes the gradient (ordered split reduction, no atomics, no zero fill)
         WinoWgrad wv{};
         wv.G = go; wv.ldg = g.ctot; wv.N = GROWTH; wv.A = Y; wv.lda = cb; wv.C = cb; wv.a_scale = bn2; wv.a_shift = bn2 + cb;
@@ -705,15 +775,7 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
         wv.Vy = at<float>(ws, n.winoVy); wv.vy_floats = n.winoVyFloats; wv.part = at<float>(ws, n.winoQ); wv.part_floats = n.winoQFloats;
         wv.B = n.B; wv.H = g.H; wv.W = g.W;
         if ((rc = launch_conv3x3_wino_wgrad(wv, side))) return rc;
-      } else {
-        if (!(n.opt_packed3x3 && n.opt_prezeroed) && (rc = zero_f32(dW3, 9 * (size_t)GROWTH * cb, side))) return rc;
-        WgradArgs w{};
-        w.g = geom3x3(n.B, g.H, g.W, 1);
-        w.G = go; w.ldg = g.ctot; w.N = GROWTH;
-        w.Xs = Y; w.ldx = cb; w.C = cb; w.x_scale = bn2; w.x_shift = bn2 + cb;
-        w.dW = dW3; w.wtap = (long)GROWTH * cb; w.ldw = cb;
-        if ((rc = launch_conv_wgrad(w, side))) return rc;
-      }
+      } else if ((rc = launch_conv_wgrad(w, side))) return rc;
       if (!n.opt_packed3x3 && (rc = launch_unpack_w(dW3, F(Gr, L.conv2), GROWTH, cb, 9, GROWTH, side))) return rc;
     }
     // ---- main: conv2 dgrad -> dZ[par], gated by relu2, with the norm2 backward reductions ----
@@ -726,37 +788,15 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
     d.Wt = w2p; d.wtap = (long)GROWTH * cb; d.ldw = cb;
     d.out = dZ; d.ldc = cb; d.M = g.M; d.N = cb;
     d.stat0 = s0; d.stat1 = s1; d.X = Y; d.ldx = cb; d.x_scale = bn2; d.x_shift = bn2 + cb;
-    // mixed-precision arithmetic on the gradient GEMMs (RDM_NET_OPT_GEMM_BF16): when all three consumers / producers of the layer's dZ -> dY
-    // tensor are the one-product kernels, it LIVES as bf16 (they round it to bf16 at staging anyway): its four passes move half the bytes
-    bool dz_bf16 = false;
-    {
-      FwdArgs e1{};
-      e1.g = geom1x1(n.B, g.H, g.W); e1.C = cb; e1.N = cin; e1.M = g.M;
-      WgradArgs w1{};
-      w1.g = geom1x1(n.B, g.H, g.W); w1.N = cb; w1.C = cin;
-      dz_bf16 = n.xs_np() == 1 && n.xs_block(b) && xs_dgrad3x3_supported(d) && xs_dgrad1x1_supported(e1) && xs_wgrad1x1_supported(w1) && g.M >= 1024 && Gr[L.conv1] != nullptr;
-    }
-    d.out_bf16 = dz_bf16;
-    // float32 mode (three products): dY leaves the norm2 backward as SPLIT ROWS when both of its consumers are the split kernels - they stage it
-    // verbatim instead of each converting and splitting every element (RDM_NET_OPT_SPLIT_ROWS)
-    bool dy_split = false, xh_split = false;
-    {
-      FwdArgs e1{};
-      e1.g = geom1x1(n.B, g.H, g.W); e1.C = cb; e1.N = cin; e1.M = g.M;
-      WgradArgs w1{};
-      w1.g = geom1x1(n.B, g.H, g.W); w1.N = cb; w1.C = cin;
-      const bool wg_ok = xs_wgrad1x1_supported(w1);
-      dy_split = n.opt_split_rows && n.xs_np() == 3 && n.xs_block(b) && g.M >= 1024 && xs_dgrad1x1_supported(e1) && (Gr[L.conv1] == nullptr || wg_ok);
-      xh_split = n.opt_split_rows && n.xs_np() == 3 && n.xs_block(b) && g.M >= 1024 && Gr[L.conv1] != nullptr && wg_ok;
-    }
-    if (n.xs_block(b) && xs_dgrad3x3_supported(d)) {
+    d.out_bf16 = enc.dz_bf16;
+    if (r.dg3_xs) {
       const bool pk = n.pk_bwd_valid && !n.xsP3[b].empty();
-      if ((rc = launch_xs_dgrad3x3(d, EPI_MASK_STATS, at<unsigned char>(ws, pk ? n.xsP3[b][i] : n.xsW), pk ? xs_dgrad3x3_workspace_bytes(cb) : n.xsWBytes, s, n.xs_np(), pk))) return rc;
+      if ((rc = launch_xs_dgrad3x3(d, EPI_MASK_STATS, at<unsigned char>(ws, pk ? n.xsP3[b][i] : n.xsW), pk ? xs_dgrad3x3_workspace_bytes(cb) : n.xsWBytes, s, r.np, pk))) return rc;
     } else if ((rc = launch_conv_fwd(d, true, EPI_MASK_STATS, s)) < 0) return rc;      // split-K layers gate + reduce atomically
     // one elementwise pass dZ := dY (BN-backward coefficients computed in the same kernel).  Forming dY inside the conv1
     // dgrad / wgrad loaders instead was measured slower (heavier loaders cost the MFMA kernels more: 155 vs 164 img/s)
     if ((rc = launch_bn_bwd_apply(dZ, cb, dZ, cb, Y, cb, s0, s1, (double)g.M, F(T, L.bn2.w), bn2 + 2 * cb, bn2 + 3 * cb,
-                                  Gr[L.bn2.w] ? F(Gr, L.bn2.w) : nullptr, Gr[L.bn2.b] ? F(Gr, L.bn2.b) : nullptr, g.M, cb, false, training, s, dz_bf16, dy_split)))
+                                  Gr[L.bn2.w] ? F(Gr, L.bn2.w) : nullptr, Gr[L.bn2.b] ? F(Gr, L.bn2.b) : nullptr, g.M, cb, false, training, s, enc.dz_bf16, enc.dy_split)))
       return rc;
     // ---- side stream: conv1 (1x1) wgrad straight into the PyTorch-layout gradient ([cb][cin][1][1]) ----
     if (Gr[L.conv1]) {
@@ -770,16 +810,17 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
       w.G = dZ; w.ldg = cb; w.N = cb;
       w.Xs = blk; w.ldx = g.ctot; w.C = cin; w.x_scale = bn1; w.x_shift = bn1 + cin;
       w.dW = F(Gr, L.conv1); w.wtap = 0; w.ldw = cin;
-      w.xsplit = n.xs_block(b) ? n.xs_np() : 0;
-      w.g_bf16 = dz_bf16;
-      w.g_split = dy_split;
-      if (xh_split) {
+      w.g_bf16 = enc.dz_bf16;
+      w.g_split = enc.dy_split;
+      if (enc.xh_split) {
         // relu1(norm1(x)) of this layer, activated and split ONCE (the GEMM re-stages its activation tile for each of its cb / 128 gradient tiles)
         float* xh = at<float>(ws, n.xsXh);
         if ((rc = launch_split_rows(blk, g.ctot, bn1, bn1 + cin, xh, cin, g.M, cin, side))) return rc;
         w.Xs = xh; w.ldx = cin; w.x_scale = nullptr; w.x_shift = nullptr; w.x_split = 1;
       }
-      if ((rc = launch_conv_wgrad(w, side))) return rc;
+      if (r.wg1_xs) { w.xsplit = r.np; rc = launch_xs_wgrad1x1(w, side); }
+      else rc = launch_conv_wgrad(w, side);
+      if (rc) return rc;
       RDM_HIP_OK(hipEventRecord(n.ev_dz[par], side));
       n.dz_busy[par] = true;
     }
@@ -792,15 +833,13 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
     e.Wt = F(T, L.conv1); e.wtap = 0; e.ldw = cin;
     e.out = dZ1; e.ldc = cin; e.M = g.M; e.N = cin;
     e.stat0 = s0; e.stat1 = s1; e.X = blk; e.ldx = g.ctot; e.x_scale = bn1; e.x_shift = bn1 + cin;
-    e.a_bf16 = dz_bf16;
-    e.a_split = dy_split;
-    const bool xs_d1 = n.xs_block(b) && xs_dgrad1x1_supported(e);
-    // deferred norm1 backward: decided once per BLOCK - a layer that did not take it would neither consume nor forward the running (b, c) sums
-    const bool defer = xs_d1 && n.opt_defer_norm1 && block_defers_norm1(n, b);
+    e.a_bf16 = enc.dz_bf16;
+    e.a_split = enc.dy_split;
+    const bool defer = R.defer;                                           // deferred norm1 backward: decided once per BLOCK
     if (defer) { e.out = G; e.ldc = g.ctot; e.acc_scaled = 1; }          // the epilogue adds (gamma * rstd) * dz into the block gradient itself
-    if (xs_d1) {
+    if (r.dg1_xs) {
       const bool pk = n.pk_bwd_valid && !n.xsP1[b].empty();
-      if ((rc = launch_xs_dgrad1x1(e, EPI_MASK_STATS, at<unsigned char>(ws, pk ? n.xsP1[b][i] : n.xsW), pk ? xs_dgrad1x1_workspace_bytes(cb, cin) : n.xsWBytes, s, n.xs_np(), pk))) return rc;
+      if ((rc = launch_xs_dgrad1x1(e, EPI_MASK_STATS, at<unsigned char>(ws, pk ? n.xsP1[b][i] : n.xsW), pk ? xs_dgrad1x1_workspace_bytes(cb, cin) : n.xsWBytes, s, r.np, pk))) return rc;
     } else if ((rc = launch_conv_fwd(e, true, EPI_MASK_STATS, s)) < 0) return rc;
     if (defer) {
       // ... the b * x + c terms of all layers are summed per channel and applied to the channels whose gradient is read next: the 48 the layer
@@ -1011,6 +1050,7 @@ int rdm_net_set_option(rdm_net* net, int32_t option, int32_t value) {
 #endif
   }
   else { set_error("rdm_net_set_option: unknown option %d", option); return RDM_ERR_BAD_ARGUMENT; }
+  if (option != RDM_NET_OPT_JOIN_PER_SEGMENT) n->routes_valid = false;       // (set before every backward; it routes nothing)
   return RDM_OK;
 }
 
@@ -1039,6 +1079,20 @@ int rdm_net_buffer(const rdm_net* net, const char* name, int64_t* offset_bytes, 
   if (!strcmp(name, "dZ1")) { *offset_bytes = n.dZ1; *numel = 0; for (int k = 0; k < 4; ++k) *numel = std::max<int64_t>(*numel, (int64_t)n.bg[k].M * n.bg[k].ctot); return RDM_OK; }
   set_error("rdm_net_buffer: unknown buffer '%s'", name);
   return RDM_ERR_BAD_ARGUMENT;
+}
+
+/* debug / test access to the plan's routing table (resolve_routes), as rdm_net_route_flags; needs no device */
+int rdm_net_route(const rdm_net* net, int32_t block, int32_t layer, int32_t conv1_has_grad, int32_t* flags) {
+  RDM_CHECK_ARG(net && flags, "NULL argument");
+  RDM_CHECK_ARG(block >= 0 && block < 4 && layer >= 0 && layer < kBlocks[block < 0 || block > 3 ? 0 : block].layers, "rdm_net_route: no layer %d in dense block %d", layer, block);
+  const BlockRoute& R = route(*const_cast<NetImpl*>(reinterpret_cast<const NetImpl*>(net)), block);      // the table is a cache of the plan: resolved on first use
+  const LayerRoute& r = R.layer[layer];
+  const Encodings& e = r.enc[conv1_has_grad != 0];
+  *flags = (R.pipelined ? RDM_ROUTE_PIPELINED : 0) | (R.raw ? RDM_ROUTE_RAW : 0) | (R.wino ? RDM_ROUTE_WINO_FWD : 0) | (R.wino_x6 ? RDM_ROUTE_WINO_X6 : 0) |
+           (R.xf ? RDM_ROUTE_XF : 0) | (R.defer ? RDM_ROUTE_DEFER : 0) | (r.wg3 == Wg3::XS ? RDM_ROUTE_WG3_XS : 0) | (r.wg3 == Wg3::WINO ? RDM_ROUTE_WG3_WINO : 0) |
+           (r.dg3_xs ? RDM_ROUTE_DG3_XS : 0) | (r.dg1_xs ? RDM_ROUTE_DG1_XS : 0) | (r.wg1_xs ? RDM_ROUTE_WG1_XS : 0) | (r.np == 1 ? RDM_ROUTE_NP1 : 0) |
+           (e.g_frame ? RDM_ROUTE_G_FRAME : 0) | (e.dz_bf16 ? RDM_ROUTE_DZ_BF16 : 0) | (e.dy_split ? RDM_ROUTE_DY_SPLIT : 0) | (e.xh_split ? RDM_ROUTE_XH_SPLIT : 0);
+  return RDM_OK;
 }
 
 /* the encoder's output (trans_e4, RDM_Net.py:94) of the last rdm_net_forward on this workspace, as (B,1056,h,w) float32 NCHW: the tensor
@@ -1093,7 +1147,7 @@ int rdm_net_forward(rdm_net* net, const float* x, void* const* T, void* ws, size
   n.pk_fwd_valid = n.pk_bwd_valid = false;
   if (n.opt_prepack && n.opt_split_fwd && !n.opt_det) {
     for (int b = 0; b < 4; ++b)
-      if (n.xf_block(b) && !n.xfP[b].empty())
+      if (route(n, b).xf && !n.xfP[b].empty())
         for (int i = 0; i < kBlocks[b].layers; ++i) {
           const int cin = kBlocks[b].cin + i * GROWTH;
           if ((rc = launch_xs_pack_w1_fwd(F(T, reg().layers[b][i].conv1), cin, n.bg[b].cb, cin, at<unsigned char>(ws, n.xfP[b][i]), n.side))) return rc;
@@ -1106,17 +1160,17 @@ int rdm_net_forward(rdm_net* net, const float* x, void* const* T, void* ws, size
       for (int i = 0; i < kBlocks[b].layers; ++i)
         if ((rc = launch_pack_w(F(T, reg().layers[b][i].conv2), at<float>(ws, n.lws[b][i].w2p), GROWTH, n.bg[b].cb, 9, GROWTH, n.side))) return rc;
   for (int b = 0; b < 4; ++b)                                 // Winograd weight transforms U = G g G^T, off the critical path like the packing
-    if (n.wino_fwd[b] && !n.opt_no_wino)
+    if (route(n, b).wino)
       for (int i = 0; i < kBlocks[b].layers; ++i) {
         const float* w2p = n.opt_packed3x3 ? F(T, reg().layers[b][i].conv2) : at<float>(ws, n.lws[b][i].w2p);
-        if ((rc = launch_wino_weight(w2p, (long)GROWTH * n.bg[b].cb, n.bg[b].cb, GROWTH, n.bg[b].cb, at<float>(ws, n.winoU[b][i]), n.side, n.wino_x6(b)))) return rc;
+        if ((rc = launch_wino_weight(w2p, (long)GROWTH * n.bg[b].cb, n.bg[b].cb, GROWTH, n.bg[b].cb, at<float>(ws, n.winoU[b][i]), n.side, route(n, b).wino_x6))) return rc;
       }
   RDM_HIP_OK(hipEventRecord(n.ev_side, n.side));
   // ... and, behind everything the forward waits for, the split / fragment-order images the BACKWARD's input-gradient kernels read (the weights
   // do not change between this forward and its backward): 108 launches that used to sit on the backward's dependent chain
   if (training && n.opt_prepack && n.opt_split_bwd && !n.opt_det) {
     for (int b = 3; b >= 0; --b)
-      if (n.xs_block(b) && !n.xsP3[b].empty())
+      if (route(n, b).xs && !n.xsP3[b].empty())
         for (int i = kBlocks[b].layers - 1; i >= 0; --i) {
           const int cin = kBlocks[b].cin + i * GROWTH, cb = n.bg[b].cb;
           const float* w2p = n.opt_packed3x3 ? F(T, reg().layers[b][i].conv2) : at<float>(ws, n.lws[b][i].w2p);

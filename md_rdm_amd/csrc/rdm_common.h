@@ -136,8 +136,8 @@ struct WgradArgs {          // dW[tap][n][c] += sum_m G[m][n] * f(Xs[pix(m,tap)]
   long n_items;                               // set by the launcher: column tiles x row tiles x splits
   unsigned g_bytes, x_bytes;                  // set by the launcher: addressable extents of G / Xs
   int xcd_flat;                               // 1: keep the hardware block order (A/B switch)
-  int xsplit;                                 // != 0: the kernels of xsplit.hip may serve this launch (gradients only): 3 (or any value but 1) = split precision,
-                                              // three bf16 MFMAs per product; 1 = operands rounded to bf16, one MFMA (the mixed-precision mode)
+  int xsplit;                                 // launch_xs_wgrad1x1 / launch_xs_wgrad3x3 (xsplit.h) only: 3 (or any value but 1) = split precision, three bf16 MFMAs
+                                              // per product; 1 = operands rounded to bf16, one MFMA (the mixed-precision mode).  launch_conv_wgrad takes 0 only
   int g_bf16;                                 // xsplit == 1 only: G is rows of bf16 (ldg in elements of that type)
   int g_split, x_split;                       // xsplit == 3, 1x1 only: G / Xs are SPLIT ROWS (xsplit_dev.h; Xs then already activated: no x_scale / x_shift)
   int g_frame;                                // xsplit == 3, 3x3 only: G is the frame image launch_frame_split_rows wrote (xsplit.h)
@@ -164,7 +164,7 @@ int launch_nyu_preprocess(const unsigned char* rgb, const float* depth, const vo
 // OVERWRITTEN dword 0 in lanes 12-15 of every 16 when a VALU write follows the store directly, and stores correctly behind one s_nop.  (Found in
 // round 4 as "wrong values in lanes 12-15" of xs_dgrad3x3_kernel's gated output.)  Every >64-bit buffer store with a runtime scalar offset goes
 // through this helper: the store and its two wait states are one asm block, so no schedule can separate them.
-// tools/store_hazard/scan_isa.py audits the compiled ISA of the whole library for the unprotected pattern (tests/test_boundary.py runs it).
+// tools/store_hazard/scan_isa.py audits the compiled ISA of the whole library for the unprotected pattern (tests/test_isa_hazard.py runs it).
 typedef unsigned int rdm_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void buffer_store_b128_soffset(rdm_u32x4 data, __amdgpu_buffer_rsrc_t srd, int voffset, int soffset) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -514,18 +514,19 @@ class DepthEstimationNet(BaseModel):
             L = _lib.lib()
             h = C.c_void_p()
             _lib.check(L.rdm_net_create(B, H, W, C.byref(h)))
-            _lib.check(L.rdm_net_set_option(h, 1, 1))         # RDM_NET_OPT_PACKED_3X3: flatten_parameters keeps the 3x3 weights packed
-            _lib.check(L.rdm_net_set_option(h, 2, 1))         # RDM_NET_OPT_GRADS_PREZEROED: _native_backward fills the flat gradient buffer once
-            if self.deterministic:
-                _lib.check(L.rdm_net_set_option(h, 4, 1))     # RDM_NET_OPT_DETERMINISTIC
-            _lib.check(L.rdm_net_set_option(h, 6, 1 if self.backward_precision == "bf16x3" else 0))     # RDM_NET_OPT_SPLIT_BWD
-            _lib.check(L.rdm_net_set_option(h, 7, 1 if self.forward_split else 0))                      # RDM_NET_OPT_SPLIT_FWD
-            _lib.check(L.rdm_net_set_option(h, 10, 1 if self.prepack else 0))                            # RDM_NET_OPT_PREPACK
-            _lib.check(L.rdm_net_set_option(h, 9, 1 if self.defer_norm1 else 0))                         # RDM_NET_OPT_DEFER_NORM1
-            _lib.check(L.rdm_net_set_option(h, 11, 1 if self.split_rows else 0))                         # RDM_NET_OPT_SPLIT_ROWS
-            _lib.check(L.rdm_net_set_option(h, 12, 1 if self.wino_x6 else 0))                            # RDM_NET_OPT_WINO_X6
-            _lib.check(L.rdm_net_set_option(h, 13, 1 if self.fuse_stats3 else 0))                        # RDM_NET_OPT_FUSE_STATS3
-            _lib.check(L.rdm_net_set_option(h, 8, int(self.gemm_bf16)))                          # RDM_NET_OPT_GEMM_BF16
+            opts = [(_lib.NET_OPT_PACKED_3X3, 1),                  # flatten_parameters keeps the 3x3 weights packed
+                    (_lib.NET_OPT_GRADS_PREZEROED, 1),             # _native_backward fills the flat gradient buffer once
+                    (_lib.NET_OPT_DETERMINISTIC, int(bool(self.deterministic))),
+                    (_lib.NET_OPT_SPLIT_BWD, int(self.backward_precision == "bf16x3")),
+                    (_lib.NET_OPT_SPLIT_FWD, int(bool(self.forward_split))),
+                    (_lib.NET_OPT_PREPACK, int(bool(self.prepack))),
+                    (_lib.NET_OPT_DEFER_NORM1, int(bool(self.defer_norm1))),
+                    (_lib.NET_OPT_SPLIT_ROWS, int(bool(self.split_rows))),
+                    (_lib.NET_OPT_WINO_X6, int(bool(self.wino_x6))),
+                    (_lib.NET_OPT_FUSE_STATS3, int(bool(self.fuse_stats3))),
+                    (_lib.NET_OPT_GEMM_BF16, int(self.gemm_bf16))]
+            for opt, value in opts:
+                _lib.check(L.rdm_net_set_option(h, opt, value))
             oh, ow = C.c_int32(), C.c_int32()
             _lib.check(L.rdm_net_output_hw(h, C.byref(oh), C.byref(ow)))
             self._plans[key] = (h, int(L.rdm_net_workspace_bytes(h)), oh.value, ow.value)
@@ -566,7 +567,7 @@ class DepthEstimationNet(BaseModel):
         gtable = (C.c_void_p * len(gt))(*gt)
         st = _lib.stream()
         # without a per-stage consumer (the data-parallel exchange) the side stream joins once per segment, not after each of the 13 stages
-        _lib.check(L.rdm_net_set_option(h, 5, 0 if self.grad_ready_hook is not None else 1))
+        _lib.check(L.rdm_net_set_option(h, _lib.NET_OPT_JOIN_PER_SEGMENT, 0 if self.grad_ready_hook is not None else 1))
         gflat.zero_()                                                # ONE fill instead of ~160 per-tensor fills inside the plan
         for stage in range(L.rdm_net_num_backward_stages()):        # ~25 MB of gradients per stage: the DP exchange starts every few layers
             _lib.check(L.rdm_net_backward_stage(h, _lib.ptr(dlogits), table, gtable, C.c_void_p(self._ws.data_ptr()), ws_bytes, stage, st))

@@ -30,6 +30,15 @@ def test_header_symbols_exported_and_bound(L):
         assert hasattr(L, name)
 
 
+def test_python_option_names_mirror_the_header_enum():
+    """_lib.NET_OPT_* (what RDM_Net.py passes to rdm_net_set_option) == rdm_net_option, names and values."""
+    from md_rdm_amd import _lib
+    body = re.search(r"typedef enum rdm_net_option \{(.*?)\} rdm_net_option;", open(HEADER).read(), re.S).group(1)
+    declared = {n: int(v) for n, v in re.findall(r"RDM_(NET_OPT_[A-Z0-9_]+)\s*=\s*(\d+)", body)}
+    assert len(declared) == 13 and sorted(declared.values()) == list(range(1, 14))
+    assert declared == {n: getattr(_lib, n) for n in dir(_lib) if n.startswith("NET_OPT_")}
+
+
 def test_bench_library_is_separate_from_the_product(L):
     """The measurement kernels live in librdm_bench.so (include/rdm_bench.h): declared == bound == exported THERE, and the product
     library exports none of them."""
