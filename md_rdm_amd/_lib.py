@@ -164,6 +164,11 @@ _BENCH_SIGNATURES = {
 }
 BENCH_LIB_PATH = os.path.join(_HERE, "librdm_bench.so")
 
+# include/rdm_viz.h: depth-map rendering, part of librdm_hip.so, declared in a header of its own
+_VIZ_SIGNATURES = {
+    "rdm_viz_rows_u8": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, f64, f64, vp, i32, vp]),
+}
+
 _lib = None
 _bench = None
 
@@ -180,9 +185,10 @@ def lib():
             raise RdmError(f"{LIB_PATH} not found - run `python -m md_rdm_amd.build` (hipcc --offload-arch=gfx950). "
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
-            fn.restype, fn.argtypes = res, args
+        for table in (_SIGNATURES, _VIZ_SIGNATURES):
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
+                fn.restype, fn.argtypes = res, args
         # development A/B switch (include/rdm_dev.h): exported by RDM_DEV_VARIANTS=1 builds only; on the shipped library the tools' calls
         # land in a Python stub that accepts 0 (= the shipped configuration) and refuses anything else
         try:
@@ -229,6 +235,10 @@ def exported_symbols():
 
 def bench_symbols():
     return list(_BENCH_SIGNATURES)
+
+
+def viz_symbols():
+    return list(_VIZ_SIGNATURES)
 
 
 def check(rc):

@@ -39,7 +39,7 @@ def build(force=False, verbose=True):
     if not os.path.exists(stamp) or open(stamp).read().strip() != mode:
         force = True
     flags = FLAGS + (["-DRDM_DEV_VARIANTS"] if mode == "dev" else [])
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", "rdm_hip.h")]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", f) for f in ("rdm_hip.h", "rdm_viz.h")]
     jobs = []
     for src in sources():
         obj = os.path.join(OBJ, src[:-4] + ".o")

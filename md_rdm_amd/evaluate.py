@@ -11,7 +11,8 @@ are the means over the samples of the per-sample values - what the reference's b
 ``--split val`` reads the samples through validation_preprocess (Resize + CenterCrop), ``--split test`` through test_preprocess
 (dataloaders/nyu.py).  ``--synthetic N`` scores N hash-generated samples instead (``synthetic_samples``).  Under WORLD_SIZE > 1 rank r scores
 samples r, r + world, ... (no sample is dropped; the shards may differ in size) and the ranks all-reduce the per-metric sums and the sample
-count once at the end; rank 0 prints and writes the result.
+count once at the end; rank 0 prints and writes the result.  ``--rows DIR`` also writes ``row_IIIII.png`` (I = the sample's index) for the first
+``--rows_max`` samples of each rank: input | normalised target | the map the metrics saw, the two maps over one colour range (md_rdm_amd.viz).
 """
 import json
 import os
@@ -40,6 +41,8 @@ def build_parser():
                    "which compares the recombination as it is (module.py:117)")
     p.add_argument("--out", type=str, default=None, help="write the result as JSON here")
     p.add_argument("--worker", default=6, type=int, help="threads that decode raw samples (--nyu_path)")
+    p.add_argument("--rows", type=str, default=None, metavar="DIR", help="write input | normalised target | prediction PNG rows here")
+    p.add_argument("--rows_max", type=int, default=16, metavar="N", help="rows written per rank: the first N samples it scores")
     return p
 
 
@@ -67,6 +70,8 @@ def main(argv=None):
         raise SystemExit("md_rdm_amd.evaluate: --batch_size must be positive")
     if args.synthetic < 0:
         raise SystemExit("md_rdm_amd.evaluate: --synthetic must be positive")
+    if args.rows_max < 0:
+        raise SystemExit("md_rdm_amd.evaluate: --rows_max must not be negative")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit(NO_GPU)
@@ -114,7 +119,13 @@ def main(argv=None):
         def batches():
             return iter(loader)
         source = args.split
-    result = harness.evaluate(model, batches(), computer, exp_pred=args.exp_pred)
+    rows = []
+    result = harness.evaluate(model, batches(), computer, exp_pred=args.exp_pred, rows_out=rows if args.rows else None, rows_max=args.rows_max)
+    if args.rows:
+        from . import viz
+        os.makedirs(args.rows, exist_ok=True)
+        for i, row in enumerate(rows):                                   # rank r scored samples r, r + world, ... in order
+            viz.write_png(os.path.join(args.rows, "row_%05d.png" % (rank + i * world)), row)
     if world > 1:
         dist.destroy_process_group()
     if rank == 0:

@@ -69,7 +69,7 @@ def validation_step(model, x, y):
     return y_hat, normalize(y)
 
 
-def evaluate(model, batches, metrics, exp_pred=False, return_maps=False):
+def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_out=None, rows_max=16):
     """Score a model on an iterable of (x, raw depth) batches of ANY batch size: per batch ``model.predict(x)`` and ONE launch from the map and
     the raw depth to a row of metric sums per sample (``MetricComputation.compute_rows``); the rows stay on the device and come over in one
     copy after the last batch.  The result, {metric: mean over the samples of the per-sample value, "n": samples}, is what the reference's
@@ -77,14 +77,24 @@ def evaluate(model, batches, metrics, exp_pred=False, return_maps=False):
     the batch size: ``validation_step``'s prediction does not depend on the target (optimize_components returns its predictions unchanged),
     so it is ``predict``'s map.  ``metrics``: a MetricComputation or a list of metric names.  Under an initialised process group every rank
     passes its own shard (unequal shards are fine) and one all-reduce of the per-metric sums and the count makes the result global.
-    ``exp_pred``: compare exp(map) - not what the reference does.  ``return_maps``: also return the (n,1,128,128) maps of this rank."""
+    ``exp_pred``: compare exp(map) - not what the reference does.  ``return_maps``: also return the (n,1,128,128) maps of this rank.
+    ``rows_out``: a list that receives, for the first ``rows_max`` samples of this rank, the (H,3W,3) uint8 host image input | normalised target
+    (``compute_rows``' target_out) | the map the metrics saw (exp of it under ``exp_pred``), rendered on the device in one launch per batch
+    (viz.comparison_rows) and copied over once per batch."""
     import torch.distributed as dist
     from .metrics import MetricComputation, mean_over_shards
     mc = metrics if isinstance(metrics, MetricComputation) else MetricComputation(list(metrics))
     rows, maps = [], []
     for x, y in batches:
         pred = model.predict(x)
-        rows.append(mc.compute_rows(pred, y, exp_pred=exp_pred))
+        want = rows_out is not None and len(rows_out) < rows_max
+        tgt = torch.empty_like(pred) if want else None
+        rows.append(mc.compute_rows(pred, y, exp_pred=exp_pred, target_out=tgt))
+        if want:
+            from . import viz
+            k = min(x.shape[0], rows_max - len(rows_out))
+            img = viz.comparison_rows(x[:k].float(), tgt[:k], (pred.exp() if exp_pred else pred)[:k])
+            rows_out.extend(img.cpu().numpy())
         if return_maps:
             maps.append(pred)
     values = mc.values_from_rows(torch.cat(rows).cpu()) if rows else []          # the one device-to-host copy

@@ -9,6 +9,8 @@ ordinary image files.  They pass through the GPU test transform of dataloaders/n
 Resize(--size)); at least 480x640 after the first resize, like the reference's test_preprocess.  ``--synthetic N`` feeds N hash-generated
 network inputs (filler.synthetic_batch) of --size instead.  One ``.npy`` per input lands in --out: the (1,128,128) float64 log map,
 float32 ``exp`` of it with --linear, resized to the frame region the network saw ((480, 640), or --size for synthetic inputs) with --full_res.
+``--png`` writes ``NAME.png`` beside each ``.npy``: the saved map in jet colours (md_rdm_amd.viz, one launch per batch), over its own range or
+over ``--png_range LO HI`` (comparable frames); ``--png_with_input`` puts the network input to its left, the map resized to the input's size.
 """
 import os
 import sys
@@ -30,7 +32,18 @@ def build_parser():
     p.add_argument("--full_res", action="store_true", help="bicubic resize of the log map to the frame region the network saw (480x640; --size for --synthetic)")
     p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N hash-generated inputs (filler.synthetic_batch) instead of files")
     p.add_argument("--relative_decoders", type=int, nargs="*", default=[], help="subset of 6 7 8 9 10, as in md_rdm_amd.train")
+    p.add_argument("--png", action="store_true", help="also write NAME.png: the saved map in jet colours (honours --linear and --full_res)")
+    p.add_argument("--png_range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="fixed colour range instead of each map's own minimum / maximum")
+    p.add_argument("--png_with_input", action="store_true", help="the .png shows input | map, the map resized to the network input's size")
     return p
+
+
+def check_png_args(args):
+    """the --png* flags' own rules; raises SystemExit"""
+    if (args.png_range is not None or args.png_with_input) and not args.png:
+        raise SystemExit("md_rdm_amd.predict: --png_range and --png_with_input need --png")
+    if args.png_range is not None and not args.png_range[0] < args.png_range[1]:
+        raise SystemExit("md_rdm_amd.predict: --png_range needs LO < HI (got %r %r)" % tuple(args.png_range))
 
 
 def load_frame(path):
@@ -60,6 +73,7 @@ def main(argv=None):
         raise SystemExit("md_rdm_amd.predict: give input files or --synthetic N (not both)")
     if args.batch_size < 1:
         raise SystemExit("md_rdm_amd.predict: --batch_size must be positive")
+    check_png_args(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -67,7 +81,7 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
 
-    from . import checkpoint, filler
+    from . import checkpoint, filler, viz
     from .dataloaders import nyu
     from .network.RDM_Net import DepthEstimationNet
     model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
@@ -108,12 +122,19 @@ def main(argv=None):
                 raise SystemExit("md_rdm_amd.predict: %s (%dx%d frame): %s" % (items[i][0], H, W, e))
             x, _ = pre(rgb, dummy, params)
             region = (480, 640)
-        out = model.predict(x, linear=args.linear, size=region if args.full_res else None).cpu().numpy()
+        maps = model.predict(x, linear=args.linear, size=region if args.full_res else None)
+        out = maps.cpu().numpy()
         dt = time.perf_counter() - t0
-        for (name, _), m in zip(items[i:j], out):
+        if args.png:
+            lo, hi = args.png_range if args.png_range is not None else (None, None)
+            pngs = (viz.comparison_rows(x, None, maps, lo, hi) if args.png_with_input else viz.colorize(maps, lo, hi)).cpu().numpy()
+        for n, ((name, _), m) in enumerate(zip(items[i:j], out)):
             k = seen.get(name, 0)
             seen[name] = k + 1
-            np.save(os.path.join(args.out, name + ("" if k == 0 else "_%d" % k) + ".npy"), m)
+            stem = os.path.join(args.out, name + ("" if k == 0 else "_%d" % k))
+            np.save(stem + ".npy", m)
+            if args.png:
+                viz.write_png(stem + ".png", pngs[n])
         print("batch of %d: %.1f images/s" % (j - i, (j - i) / dt), flush=True)
         i = j
     return 0
