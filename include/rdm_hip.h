@@ -53,8 +53,6 @@ int rdm_profile_read(double* conv_ms_sum, double* conv_ms_union, double* conv_fl
 int rdm_profile_kind(int32_t kind, const char** name, double* ms_sum, double* flops, int32_t* launches);
 /* algorithmic HBM bytes (operands read once + result written once) of those launches; kept for the bf16 kernels (0 for the f32 kinds) */
 double rdm_profile_kind_bytes(int32_t kind);
-/* (The development A/B switch of earlier rounds is NOT part of this ABI: it is declared in include/rdm_dev.h and exists only in libraries
- * built with RDM_DEV_VARIANTS=1; the shipped library does not export it.) */
 /* number of kernel-launching calls the library has made in this process (monotonic; bench.py reports the per-step difference;
  * a K-split launcher that also enqueues its zero-fill or reduction counts once per enqueued kernel family) */
 int64_t rdm_launch_count(void);

@@ -177,6 +177,11 @@ class RdmError(RuntimeError):
     pass
 
 
+def _debug_variant_removed(v):
+    if int(v) != 0:                                 # bench.py still passes RDM_VARIANT through: 0 is the one configuration there is
+        raise RdmError(f"rdm_debug_variant({int(v)}): the development A/B switch was removed - the library has one configuration (0)")
+
+
 def lib():
     """The loaded library; raises (never falls back) when it is absent."""
     global _lib
@@ -189,16 +194,7 @@ def lib():
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
-        # development A/B switch (include/rdm_dev.h): exported by RDM_DEV_VARIANTS=1 builds only; on the shipped library the tools' calls
-        # land in a Python stub that accepts 0 (= the shipped configuration) and refuses anything else
-        try:
-            dv = getattr(L, "rdm_debug_variant")
-            dv.restype, dv.argtypes = None, [i32]
-        except AttributeError:
-            def _no_variants(v):
-                if int(v) != 0:
-                    raise RdmError(f"rdm_debug_variant({int(v)}): this library was built without RDM_DEV_VARIANTS - rebuild with RDM_DEV_VARIANTS=1 python -m md_rdm_amd.build")
-            L.rdm_debug_variant = _no_variants
+        L.rdm_debug_variant = _debug_variant_removed
         _lib = L
     return _lib
 

@@ -30,15 +30,8 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    """RDM_DEV_VARIANTS=1 in the environment compiles the development A/B switch in (rdm_debug_variant); the default ("ship") build has
-    none.  Switching mode rebuilds everything."""
     os.makedirs(OBJ, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    mode = "dev" if os.environ.get("RDM_DEV_VARIANTS", "0") not in ("", "0") else "ship"
-    stamp = os.path.join(OBJ, ".mode")
-    if not os.path.exists(stamp) or open(stamp).read().strip() != mode:
-        force = True
-    flags = FLAGS + (["-DRDM_DEV_VARIANTS"] if mode == "dev" else [])
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", f) for f in ("rdm_hip.h", "rdm_viz.h")]
     jobs = []
     for src in sources():
@@ -48,7 +41,7 @@ def build(force=False, verbose=True):
 
     def compile_one(job):
         src, obj = job
-        cmd = [hipcc] + flags + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc] + FLAGS + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{r.stderr}")
@@ -65,7 +58,7 @@ def build(force=False, verbose=True):
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stderr}")
         if verbose:
-            print(f"[build] linked {LIB} ({mode})", flush=True)
+            print(f"[build] linked {LIB}", flush=True)
     # the development tools' measurement kernels: their own library next to the product, resolving set_error / the launch counter from it
     bsrcs = sorted(f for f in os.listdir(BENCH_SRC) if f.endswith(".hip")) if os.path.isdir(BENCH_SRC) else []
     bobjs = []
@@ -73,7 +66,7 @@ def build(force=False, verbose=True):
         obj = os.path.join(OBJ, "bench_" + src[:-4] + ".o")
         bobjs.append(obj)
         if force or _stale(obj, [os.path.join(BENCH_SRC, src)] + headers + [os.path.join(HERE, "..", "include", "rdm_bench.h")]):
-            r = subprocess.run([hipcc] + flags + ["-c", os.path.join(BENCH_SRC, src), "-o", obj], capture_output=True, text=True)
+            r = subprocess.run([hipcc] + FLAGS + ["-c", os.path.join(BENCH_SRC, src), "-o", obj], capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError(f"hipcc failed on bench/{src}:\n{r.stderr}")
             if verbose:
@@ -85,8 +78,6 @@ def build(force=False, verbose=True):
             raise RuntimeError(f"link failed:\n{r.stderr}")
         if verbose:
             print(f"[build] linked {BENCH_LIB}", flush=True)
-    with open(stamp, "w") as fh:
-        fh.write(mode)
     return LIB
 
 

@@ -8,9 +8,6 @@
 #include <vector>
 
 #include "rdm_common.h"
-#ifdef RDM_DEV_VARIANTS
-#include "../../include/rdm_dev.h"
-#endif
 #include "elementwise.h"
 #include "bf16.h"
 #include "wino.h"
@@ -63,9 +60,6 @@ extern "C" {
 const char* rdm_last_error_string(void) { return g_err; }
 int rdm_version(void) { return 100; }
 
-#ifdef RDM_DEV_VARIANTS
-void rdm_debug_variant(int32_t v) { rdm::g_variant = v; }      // include/rdm_dev.h: development builds only
-#endif
 int64_t rdm_launch_count(void) { return rdm::g_launches; }
 void rdm_census_enable(int32_t on) { rdm::g_census_on = on != 0; }
 void rdm_census_reset(void) {

@@ -12,7 +12,6 @@ struct GemmBf16Args {        // out[m][n] = bias[n] + sum_k f(X[m][k]) * W[n][k]
   const float* oscale; const float* oshift; // optional f32[N]: out = relu(out*oscale[n] + oshift[n]) before the bf16 rounding (the CONSUMER's eval-mode BatchNorm + ReLU)
   float* partial; size_t partial_floats;   // optional f32 scratch for a K-split ([split][M][N] partial sums + one tiny reduction launch)
   unsigned x_bytes, w_bytes, p_bytes, o_bytes;   // set by the launcher (buffer descriptors)
-  int abl;                                 // development builds: ablation bits (0 in the shipped build)
   // training-mode statistics epilogue (osum != NULL; gemm_bf16_kernel<..., STATS = true>, no panel kernel, no oscale): per-channel sum and sum of
   // squares of the STORED (bf16-rounded) outputs - f32 per wave row tile into `stats` ([tile][sum N | sq N]), combined in f64 in tile order
   double* osum; double* osq;
@@ -43,7 +42,6 @@ struct Conv3ActArgs {        // out[m][n] = sum_{tap,c} Y[pix(m,tap)][c] * w[n][
   unsigned* counters; int n_counters;      // one per tile, ZERO on entry, left zero (needed when partial != NULL)
   int split, slots, tiles_per_img, rect;   // set by the launcher (rect: 64-column rectangular tiles for rows too wide for whole-row tiles)
   unsigned y_bytes, w_bytes;
-  int abl;                                 // development builds: ablation bits (0 in the shipped build)
 };
 
 int launch_gemm_bf16(const GemmBf16Args& a, bool out_f32, hipStream_t s);

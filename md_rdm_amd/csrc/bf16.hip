@@ -295,11 +295,6 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff
 // tiled kernel takes 150 - the weight stream alone, 377 MB through L2 -> LDS per launch, took 70 us.  256-row panels halve it.)
 // ---------------------------------------------------------------------------------------------
 constexpr int PANEL_STEP = 96 * 128, PANEL_EPI = 2048;
-#ifdef RDM_DEV_VARIANTS
-#define RDM_STAMP(v) const long v = __builtin_readcyclecounter()
-#else
-#define RDM_STAMP(v)
-#endif
 
 template <int NKK>            // 32-deep K half-steps per item: 32 (NKK - 1) < K <= 32 NKK (compile-time: the multiply loop is one straight-line block)
 __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p) {
@@ -354,9 +349,6 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
 #pragma unroll
       for (int j = 0; j < 6; ++j) wf[set][j] = *reinterpret_cast<const bf16x8*>(wrd + (kk >> 1) * PANEL_STEP + j * 2048 + ((((unsigned)((kk & 1) * 4 + g)) ^ sw) << 4));
     };
-#ifdef RDM_DEV_VARIANTS
-    if (p.abl & 4) return;
-#endif
     constexpr bool DB = true;                                            // (long K: the activations take the registers of the second fragment set)
     frags(0, 0);
 #pragma unroll
@@ -385,10 +377,7 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int m = m0 + i * 16 + l16;
-      bool ok = slot >= 0 && m < p.M;
-#ifdef RDM_DEV_VARIANTS
-      if (p.abl & 1) ok = false;
-#endif
+      const bool ok = slot >= 0 && m < p.M;
       rowoff[i] = ok ? ((unsigned)m * (unsigned)p.ldc + (unsigned)(n0 + g * 4)) * 2u : OOB;
     }
 #pragma unroll
@@ -452,25 +441,13 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
       }
     }
     // this item's pieces have landed: behind them this wave issued exactly the previous item's 12 stores (nothing before the first item)
-    RDM_STAMP(t0);
     if (item == it0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
-    RDM_STAMP(t1);
     __builtin_amdgcn_s_barrier();                                       // ... everybody's have; every wave is past the other buffer (item - 1)
     asm volatile("" ::: "memory");
-    RDM_STAMP(t2);
     if (item + 1 < it1) request(item + 1);
-    RDM_STAMP(t3);
     mma(item);
-    RDM_STAMP(t4);
     epilogue(m0, n0, item);
-#ifdef RDM_DEV_VARIANTS
-    if ((p.abl & 8) && p.partial && blockIdx.x == 3 && lane == 0) {     // tools/panel_gemm_stamps.py: cycles per phase, per wave of one workgroup
-      RDM_STAMP(t5);
-      float* d = p.partial + wave * 8;
-      d[0] += (float)(t1 - t0); d[1] += (float)(t2 - t1); d[2] += (float)(t3 - t2); d[3] += (float)(t4 - t3); d[4] += (float)(t5 - t4); d[5] += 1.f;
-    }
-#endif
   }
 }
 
@@ -726,15 +703,9 @@ __global__ __launch_bounds__(NC * 128, 2) void conv3x3_act_bf16_kernel(Conv3ActA
       unsigned char* const ib = smem + st * ACT_IMG_BYTES;
       unsigned char* const wb = smem + 2 * ACT_IMG_BYTES + st * ACT_W_BYTES;
       const unsigned so = (unsigned)cs * 64u, wso = (unsigned)cs * (unsigned)ACT_W_BYTES;
-#ifdef RDM_DEV_VARIANTS
-      if (!(p.abl & 1))
-#endif
 #pragma unroll
       for (int i = 0; i < HP; ++i)
         if (lw + i * NC < npieces) dma16(srdY, voff[i], so, ib + (lw + i * NC) * 1024);
-#ifdef RDM_DEV_VARIANTS
-      if (!(p.abl & 2))
-#endif
 #pragma unroll
       for (int q = 0; q < WP; ++q)
         if (lw + q * NC < WPIECES) dma16(srdW, wvoff + (unsigned)((lw + q * NC) * 1024), wso, wb + (lw + q * NC) * 1024);
@@ -807,19 +778,14 @@ __global__ __launch_bounds__(NC * 128, 2) void conv3x3_act_bf16_kernel(Conv3ActA
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-#ifdef RDM_DEV_VARIANTS
-    const bool work = active && !(p.abl & 4);
-#else
-    const bool work = active;
-#endif
     for (int cs = cs0; cs < cs1; cs += 2) {                            // stages alternate in straight-line code (accumulation stays in place)
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (work) slab(std::integral_constant<int, 0>{});
+      if (active) slab(std::integral_constant<int, 0>{});
       if (cs + 1 < cs1) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (work) slab(std::integral_constant<int, 1>{});
+        if (active) slab(std::integral_constant<int, 1>{});
       }
     }
   }
@@ -1180,10 +1146,7 @@ int launch_gemm_bf16(const GemmBf16Args& a_in, bool out_f32, hipStream_t s) {
   // Wave quantisation: 512 workgroups are resident (2 per CU).  dense_e3 (M = 8816, N = 1408) has 1035 tiles of 128 x 96 - three rounds,
   // the third with 11 workgroups - but 897 of 128 x 112 (4 waves x 32 rows x 112 columns: 56 accumulators): two.  Cost = rounds x tile area.
   const long t112 = (long)cdiv(a.M, 128) * cdiv(a.N, 112);
-  bool wide112 = cdiv(t112, 512L) * 112 < cdiv(t96, 512L) * 96 && t96 <= 4096;
-#ifdef RDM_DEV_VARIANTS
-  if (g_variant == 304) wide112 = false;
-#endif
+  const bool wide112 = cdiv(t112, 512L) * 112 < cdiv(t96, 512L) * 96 && t96 <= 4096;
   // few pixels (decoder: 640 rows) and a long K: split K over grid.z so the chip is not left to ~80 workgroups
   int split = 1;
   const long small_blocks = (long)cdiv(a.M, 32) * cdiv(a.N, 96);
@@ -1205,9 +1168,6 @@ int launch_gemm_bf16(const GemmBf16Args& a_in, bool out_f32, hipStream_t s) {
   // (measured at M = 2280: 64x48 / 64x96 / 128x48 / 128x96 tiles and 2 vs 4 register stages all land at 21-26 us - the kernel is
   // bound by instruction issue, ~140 non-MFMA instructions per 64-deep step of which the BN-ReLU staging transform is the largest part)
   // many pixels x many outputs x short K (dense_e2): the persistent panel kernel
-#ifdef RDM_DEV_VARIANTS
-  a.abl = g_variant >= 200 && g_variant < 216 ? g_variant - 200 : 0;
-#endif
   // (at dense_e3's 525 items - two per workgroup - it only ties the tiled kernel: 37.3 vs 37.0 us at K = 336)
   int stat_rows = 0;
   const bool panel = !stats && !out_f32 && !a.bias && split == 1 && a.K <= 352 && a.M >= 8192 && a.N >= 1024 && (long)cdiv(a.M, 256) * cdiv(a.N, 96) >= 1024;
@@ -1403,9 +1363,6 @@ int launch_conv3x3_act_bf16(const Conv3ActArgs& a_in, hipStream_t s) {
     return RDM_ERR_UNSUPPORTED;
   }
   a.split = pl.split; a.slots = ACT_MAX_SLOTS; a.tiles_per_img = pl.tpi; a.rect = pl.rect;
-#ifdef RDM_DEV_VARIANTS
-  a.abl = g_variant >= 100 && g_variant < 116 ? g_variant - 100 : 0;
-#endif
   void* tk = profile_begin(s, 2.0 * M * 48.0 * a.C * 9.0, 12, 2.0 * ((double)M * a.C + 9.0 * 48 * a.C + (double)M * 48));
   dim3 grid((unsigned)(a.B * pl.tpi), (unsigned)pl.split);
 #define RDM_C3A(NC_)                                                                                                                      \

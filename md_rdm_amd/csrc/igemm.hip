@@ -917,10 +917,6 @@ int profile_kind(int kind, const char** name, double* ms_sum, double* flops, int
 // ---------------------------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------------------------
-#ifdef RDM_DEV_VARIANTS
-int g_variant = 0;      // A/B switch for in-process kernel comparisons (rdm_debug_variant)
-#endif
-
 static const char* epi_name(int e) {
   static const char* const n[5] = {"STORE", "STORE_STATS", "MASK_STATS", "ATOMIC", "MASK_STATS_ATOMIC"};
   return e >= 0 && e < 5 ? n[e] : "?";
@@ -1006,8 +1002,8 @@ static int launch_conv_fwd_impl(const FwdArgs& a_in, bool b_kstrided, Epilogue e
   if (a.M <= 64) cfg = 2;
   // few rows (dense_e4: 4560, decoder: 1280): 128 x 48 tiles give 4x the workgroups of 256 x 48 before any split-K and no ragged
   // column tile; measured 20-45 % faster than 256 x 48 + deeper split-K on the 1x1 convs of those blocks (64 x 96 ties)
-  if (!taps && a.M <= 32768 && a.M > 64 && g_variant != 16) cfg = 3;
-  if (!taps && cfg == 0 && g_variant != 20) cfg = 3;       // also at dense_e2 size: 1x1 dgrad 121.1 vs 116.3 TFLOP/s
+  if (!taps && a.M <= 32768 && a.M > 64) cfg = 3;
+  if (!taps && cfg == 0) cfg = 3;       // also at dense_e2 size: 1x1 dgrad 121.1 vs 116.3 TFLOP/s
   // (a 64x96 wave tile - 256x96 block, 2 waves/SIMD - was measured: +1 % on the 1x1 forward, -21 % on the 3x3 dgrad)
   const long tiles = cfg == 0 ? t0 : cfg == 1 ? t1 : cfg == 2 ? (long)cdiv(a.M, 64) * cdiv(a.N, 96) : (long)cdiv(a.M, 128) * cdiv(a.N, 48);
   int split = a.split_k > 0 ? a.split_k : pick_split_k(tiles, kslabs, 256 * 4);
@@ -1021,7 +1017,7 @@ static int launch_conv_fwd_impl(const FwdArgs& a_in, bool b_kstrided, Epilogue e
     if (int zrc = launch_zero_rows(a.out, a.M, a.N, a.ldc, s)) return zrc;
   }
   a.split_k = split;
-  a.xcd_flat = g_variant == 11 || a.N <= 48;      // a single column tile has nothing to share (and the 3x3 forward measured 4 % slower remapped)
+  a.xcd_flat = a.N <= 48;      // a single column tile has nothing to share (and the 3x3 forward measured 4 % slower remapped)
   {
     const long npix = (long)a.g.B * a.g.H * a.g.W, nt = taps ? a.g.KH * a.g.KW : 1;
     const long ab = ((npix - 1) * a.lda + a.C) * 4;
@@ -1033,14 +1029,14 @@ static int launch_conv_fwd_impl(const FwdArgs& a_in, bool b_kstrided, Epilogue e
   prof.kind = b_kstrided ? 1 : 0;
 
   const bool halo_fwd = !b_kstrided && a.g.dir == 1, halo_dgrad = b_kstrided && a.g.dir == -1;
-  if ((halo_fwd || halo_dgrad) && g_variant != 7 && taps && a.g.KH == 3 && a.g.KW == 3 && a.g.SH == 1 && a.g.SW == 1 && a.g.PH == 1 && a.g.PW == 1 &&
+  if ((halo_fwd || halo_dgrad) && taps && a.g.KH == 3 && a.g.KW == 3 && a.g.SH == 1 && a.g.SW == 1 && a.g.PH == 1 && a.g.PW == 1 &&
       a.g.H == a.g.Ho && a.g.W == a.g.Wo && 2 * (a.g.W + 1) <= 256 &&   // halo <= 512 pixels = 8 float4 per thread
       (long)a.g.B * a.g.H * a.g.W < (1L << 30)) {
     prof.kind = halo_dgrad ? 3 : 2;
     // LDS halo kernel; K is split over whole channel slabs (a split keeps its 9-tap groups together).
     // `epi` / `split` were already resolved above (split > 1 => atomic epilogue, output zeroed).
     // few pixels (dense_e4, decoder): 128-pixel tiles double the workgroups before any split
-    const bool small = a.M <= 8192 && 128 + 2 * (a.g.W + 1) <= 256 && g_variant != 21;
+    const bool small = a.M <= 8192 && 128 + 2 * (a.g.W + 1) <= 256;
     const int bm = small ? 128 : 256;
     // the split chosen above (for the generic tiling) is kept for 128-pixel tiles too: re-picking it for the doubled tile count
     // was measured at whole-step level and lost (81.5 vs 79.0 ms/step at NYU B=16)
@@ -1052,7 +1048,7 @@ static int launch_conv_fwd_impl(const FwdArgs& a_in, bool b_kstrided, Epilogue e
       // tools/fetch_calibration.py): L2 fills of the main loop 1.22 GB -> 0.18 GB per launch, whole kernel 2.55x -> 1.21x its
       // compulsory bytes; the time does not move (1.468 ms either way - the kernel is bound by instruction issue, not by the fabric).
       const double w_total = (double)a.N * 9.0 * a.C * 4.0, a_tile = (double)(bm + 2 * (a.g.W + 1)) * a.C * 4.0;
-      if (!a.xcd_flat && sp == 1 && g_variant != 29 && w_total > 2.5e6 && 8.0 * a_tile <= 2.0e6) a.xcd_flat = 8;
+      if (!a.xcd_flat && sp == 1 && w_total > 2.5e6 && 8.0 * a_tile <= 2.0e6) a.xcd_flat = 8;
     }
     dim3 grid(cdiv(a.N, 48), cdiv(a.M, bm), sp);
     const int hl = cdiv(bm + 2 * (a.g.W + 1), 64);           // 256-pixel tiles: 5 (W <= 31) .. 8 (<= 127); 128-pixel tiles: 3, 4
@@ -1093,11 +1089,11 @@ static int launch_conv_fwd_impl(const FwdArgs& a_in, bool b_kstrided, Epilogue e
   // 100.4 / 108.0 / 112.5 / 115.0 vs 95.2 / 101.4 / 104.3 / 105.8 TFLOP/s (+5.5 .. 8.7 %); at dense_e2 size (69 312 pixels, K <= 336)
   // the two are level (109.5 vs 110.6 at K = 336), so the 128 x 96 register-staged kernel stays there.
   if (!taps && !b_kstrided && split == 1 && (epi == EPI_STORE || epi == EPI_STORE_STATS) && !a.add_out && a.bias == nullptr && a.M >= 16384 && a.M < 32768 &&
-      a.N >= 512 && g_variant != 38) {
+      a.N >= 512) {
     // 512 workgroups are resident (2 per CU): dense_e3 at B = 16 has 759 tiles of 256 x 128 - a full round and a half-empty one - but 1012
     // of 192 x 128: two nearly full rounds of workgroups that are a quarter shorter.  Cost = rounds x tile rows.
     const long t256 = (long)cdiv(a.N, 128) * cdiv(a.M, 256), t192 = (long)cdiv(a.N, 128) * cdiv(a.M, 192);
-    const bool m192 = cdiv(t192, 512L) * 192 < cdiv(t256, 512L) * 256 && g_variant != 39;
+    const bool m192 = cdiv(t192, 512L) * 192 < cdiv(t256, 512L) * 256;
     dim3 grid(cdiv(a.N, 128), cdiv(a.M, m192 ? 192 : 256), 1);
     const bool bn = a.a_scale != nullptr;
     RDM_CENSUS("conv1x1_dma256_kernel/%s/bn%d%s", epi_name(epi), bn ? 1 : 0, m192 ? "/m192" : "");
@@ -1164,9 +1160,9 @@ int launch_conv_wgrad(const WgradArgs& a_in, hipStream_t s) {
   const bool narrow = a.N <= 48;                      // 3x3 convs of the dense layers: 48 output channels
   // a ragged last column tile of the 128 x 96 config wastes up to 25 % of the MFMAs (C = 144: 2 x 96); 256 x 48 tiles fit every
   // C that is a multiple of 48 (PMC: the 1x1 wgrad ran its MFMA pipe at 78 % for 66 % useful - the gap was this waste)
-  const bool tall = !narrow && g_variant != 13 && a.C % 96 != 0 && (double)cdiv(a.C, 96) * 96 > 1.04 * a.C;
+  const bool tall = !narrow && a.C % 96 != 0 && (double)cdiv(a.C, 96) * 96 > 1.04 * a.C;
   // few pixels to contract over (dense_e4, decoder): half-size tiles (1x1: 93 vs 116 us at M = 4560, C = 1224; 3x3: 47 vs 55 us)
-  const bool few = Mpix <= 8192 && g_variant != 23;
+  const bool few = Mpix <= 8192;
   const long tiles = few ? (narrow ? (long)cdiv(a.C, 128) * cdiv(a.N, 48) : (long)cdiv(a.C, 48) * cdiv(a.N, 128)) * ntaps :
                      narrow ? (long)cdiv(a.C, 256) * cdiv(a.N, 48) * ntaps : tall ? (long)cdiv(a.C, 48) * cdiv(a.N, 256) * ntaps : (long)cdiv(a.C, 96) * cdiv(a.N, 128) * ntaps;
   // (rounds 1-3 had a dedicated 3x3 "row" kernel for >= 16 K pixels here - one kernel row of taps per block; the plan's many-pixel blocks moved to
@@ -1178,7 +1174,7 @@ int launch_conv_wgrad(const WgradArgs& a_in, hipStream_t s) {
     if (gb >= 0xFFFFFFFFL || xb >= 0xFFFFFFFFL) { set_error("wgrad: operand extent >= 4 GiB is not supported by the 32-bit buffer addressing"); return RDM_ERR_UNSUPPORTED; }
     a.g_bytes = (unsigned)gb; a.x_bytes = (unsigned)xb;
   }
-  a.xcd_flat = g_variant == 11;
+  a.xcd_flat = 0;
   ProfScope prof(s, 2.0 * (double)Mpix * a.N * a.C * ntaps);
   prof.kind = taps ? 5 : 4;
   RDM_CENSUS("%s/%s/%s", taps ? "conv_wgrad_kernel/taps" : "conv_wgrad_kernel/1x1",

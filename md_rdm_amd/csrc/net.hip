@@ -161,26 +161,30 @@ struct BlockRoute {
 // The weight-gradient stream is ONE per device for the whole process, shared by every plan: the runtime maps streams onto a handful of hardware
 // queues round-robin, and with a stream per plan the FOURTH plan of a process got the hardware queue of the caller's stream - its weight
 // gradients then ran in series with the dgrad chain (71 ms instead of 52 ms per step, measured) although nothing in the program had changed.
-static hipStream_t shared_side_stream(bool default_priority) {
+static hipStream_t shared_side_stream() {
   static std::mutex mu;
-  static hipStream_t streams[2][64] = {};
+  static hipStream_t streams[64] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
   std::lock_guard<std::mutex> lock(mu);
-  hipStream_t& s = streams[default_priority ? 1 : 0][dev];
+  hipStream_t& s = streams[dev];
   if (!s) {
     // lowest priority: the side stream carries bulk work (weight gradients) that should fill what the dependent chain on the
     // caller's stream leaves free, not compete with it for workgroup slots
     int prio_least = 0, prio_greatest = 0;
     hipError_t e = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    if (e == hipSuccess) e = default_priority ? hipStreamCreateWithFlags(&s, hipStreamNonBlocking) : hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio_least);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio_least);
     if (e != hipSuccess) { set_error("side stream: %s", hipGetErrorString(e)); s = nullptr; }
   }
   return s;
 }
 
-// pixel counts from which layout() sizes the per-layer pack buffers of the split kernels; resolve_routes() can never select below them
-constexpr int XS_LAYOUT_MIN_PIXELS = 1024, XF_LAYOUT_MIN_PIXELS = 8192;
+// pixel counts from which layout() sizes the per-layer pack buffers of the split kernels and resolve_routes() selects them.
+// Blocks whose gradient GEMMs run the split-precision kernels: measured per block at B=16 228x304 - dense_e4 (4 560 pixels) gains on the 1x1
+// weight / input gradients and the 3x3 input gradient (173 -> 100, 134 -> 86, 63 -> 45 us per layer) but not on the 3x3 weight gradient (51 -> 56 us:
+// XS_WG3_MIN_PIXELS); the decoder (1 280 pixels) lost overall while every layer paid two weight-pack launches and the norm1 pass on its chain (53.3 vs
+// 52.6 ms per step); with RDM_NET_OPT_PREPACK and RDM_NET_OPT_DEFER_NORM1 it gains (49.8-50.1 vs 50.4-50.7): the threshold is the kernels' own minimum
+constexpr int XS_LAYOUT_MIN_PIXELS = 1024, XF_LAYOUT_MIN_PIXELS = 8192, XS_WG3_MIN_PIXELS = 8192;
 
 struct NetImpl {
   int B, H0, W0, H1, W1;
@@ -199,7 +203,7 @@ struct NetImpl {
   bool dz_busy[2] = {false, false};
   int ensure_side() {
     if (side) return 0;
-    side = shared_side_stream(g_variant == 14);
+    side = shared_side_stream();
     if (!side) return RDM_ERR_HIP;
     RDM_HIP_OK(hipEventCreateWithFlags(&ev_go, hipEventDisableTiming));
     RDM_HIP_OK(hipEventCreateWithFlags(&ev_dy, hipEventDisableTiming));
@@ -241,11 +245,6 @@ struct NetImpl {
   int opt_packed3x3 = 0;       // RDM_NET_OPT_PACKED_3X3: the 78 3x3 weights (and their gradients) are handed over as [tap][out][in]
   int opt_prezeroed = 0;       // RDM_NET_OPT_GRADS_PREZEROED: every gradient tensor is zero when backward stage 0 starts
   int opt_split_bwd = 0;       // RDM_NET_OPT_SPLIT_BWD: the backward GEMMs of the many-pixel blocks run the split-precision (bf16x3) kernels of xsplit.hip
-  // blocks whose gradient GEMMs run the split-precision kernels: measured per block at B=16 228x304 - dense_e4 (4 560 pixels) gains on the 1x1
-  // weight / input gradients and the 3x3 input gradient (173 -> 100, 134 -> 86, 63 -> 45 us per layer) but not on the 3x3 weight gradient (51 -> 56 us);
-  // the decoder (1 280 pixels) lost overall while every layer paid two weight-pack launches and the norm1 pass on its chain (53.3 vs 52.6 ms per step);
-  // with RDM_NET_OPT_PREPACK and RDM_NET_OPT_DEFER_NORM1 it gains (49.8-50.1 vs 50.4-50.7): the threshold is the kernels' own minimum
-  int xs_min_pixels = XS_LAYOUT_MIN_PIXELS;
   int opt_split_rows = 1;      // RDM_NET_OPT_SPLIT_ROWS: dY and relu1(norm1(x)) reach the split 1x1 gradient kernels as SPLIT ROWS (xsplit_dev.h) written once by their producers
   size_t xsGf = 0;             // frame image of the layer's 48-channel output gradient for the split 3x3 weight gradient (side stream: one at a time)
   size_t xsXh = 0;             // split rows of the activation operand of the layer whose 1x1 weight gradient is running (side stream: one at a time)
@@ -254,12 +253,9 @@ struct NetImpl {
                                // value bits: 1 = the forward GEMMs, 2 = the gradient GEMMs (3 = both)
   int opt_fuse_stats3 = 1;     // RDM_NET_OPT_FUSE_STATS3: the K-split 3x3 conv of the few-pixel blocks takes the channel statistics of its output in the same launch
   int opt_split_fwd = 0;       // RDM_NET_OPT_SPLIT_FWD: conv1 of the many-pixel blocks on the three-way-split bf16x6 forward kernel
-  int xf_min_pixels = XF_LAYOUT_MIN_PIXELS;
-  int xs_wg3_min_pixels = 8192;
   // the routing table: options arrive after plan(), so route() resolves it on first use and again after rdm_net_set_option
   BlockRoute routes[4];
   bool routes_valid = false;
-  int routes_variant = 0;      // development builds: the rdm_debug_variant value the table was resolved under
   // ---- reduced-precision forward (bf16.hip): prepared-weight buffer layout + activation workspace layout ----
   struct Bf16Layer { size_t w1, w3, bn1, bn2; };
   std::vector<Bf16Layer> bfl[4];
@@ -477,18 +473,18 @@ void resolve_routes(NetImpl& n) {
     const int layers = kBlocks[b].layers;
     BlockRoute& R = n.routes[b];
     // part A / part B of a pipelined conv1 add atomically: not in deterministic mode
-    R.pipelined = !fuse_stats(g.M, g.cb) && layers > 1 && g_variant != 8 && !n.opt_det;
+    R.pipelined = !fuse_stats(g.M, g.cb) && layers > 1 && !n.opt_det;
     R.wino = n.wino_fwd[b] && !n.opt_no_wino;
     R.wino_x6 = R.wino && n.opt_wino_x6 && n.opt_split_fwd && !n.opt_det;
     R.raw = R.pipelined && g.cb <= RAWBN_MAX_C && !R.wino && g.M <= 8192 && 2 * (g.W + 1) <= 128;
-    R.xf = n.opt_split_fwd && !n.opt_det && g.M >= n.xf_min_pixels;
-    R.xs = n.opt_split_bwd && !n.opt_det && g.M >= n.xs_min_pixels;
+    R.xf = n.opt_split_fwd && !n.opt_det && g.M >= XF_LAYOUT_MIN_PIXELS;
+    R.xs = n.opt_split_bwd && !n.opt_det && g.M >= XS_LAYOUT_MIN_PIXELS;
     R.defer = R.xs && n.opt_defer_norm1;
     WgradArgs w3{};
     w3.g = geom3x3(n.B, g.H, g.W, 1); w3.N = GROWTH; w3.C = g.cb;
     FwdArgs d3{};
     d3.g = geom3x3(n.B, g.H, g.W, -1); d3.C = GROWTH; d3.N = g.cb; d3.M = g.M;
-    const Wg3 wg3 = R.xs && g.M >= n.xs_wg3_min_pixels && xs_wgrad3x3_supported(w3) ? Wg3::XS : n.wino_wg[b] && !n.opt_no_wino ? Wg3::WINO : Wg3::DIRECT;
+    const Wg3 wg3 = R.xs && g.M >= XS_WG3_MIN_PIXELS && xs_wgrad3x3_supported(w3) ? Wg3::XS : n.wino_wg[b] && !n.opt_no_wino ? Wg3::WINO : Wg3::DIRECT;
     const bool dg3_xs = R.xs && xs_dgrad3x3_supported(d3);
     R.layer.assign(layers, LayerRoute{});
     for (int i = 0; i < layers; ++i) {
@@ -519,11 +515,10 @@ void resolve_routes(NetImpl& n) {
     }
   }
   n.routes_valid = true;
-  n.routes_variant = g_variant;
 }
 
 const BlockRoute& route(NetImpl& n, int b) {
-  if (!n.routes_valid || n.routes_variant != g_variant) resolve_routes(n);
+  if (!n.routes_valid) resolve_routes(n);
   return n.routes[b];
 }
 
@@ -630,7 +625,7 @@ int forward_block(NetImpl& n, int b, void* ws, void* const* T, int training, hip
     if (pipelined && i > 0) {
       if (!raw && (rc = finalize_norm1(n, b, i, cin - GROWTH, cin, false, ws, T, training, s))) return rc;
       RDM_HIP_OK(hipStreamWaitEvent(s, n.ev_fa[i & 1], 0));
-      if (training && g_variant != 36) {
+      if (training) {
         // part B is three K-slabs and runs unsplit: its epilogue adds part A's finished sum, stores the final value and takes
         // the channel statistics of it - no separate reduction pass over Y on the critical path (it took 56 us beside part A)
         if ((rc = conv1_range(n, b, i, cin - GROWTH, cin, false, true, ws, T, s, true, raw))) return rc;
@@ -1018,37 +1013,14 @@ int rdm_net_set_option(rdm_net* net, int32_t option, int32_t value) {
   else if (option == RDM_NET_OPT_DIRECT_3X3) n->opt_no_wino = value != 0;
   else if (option == RDM_NET_OPT_DETERMINISTIC) n->opt_det = value != 0;
   else if (option == RDM_NET_OPT_JOIN_PER_SEGMENT) n->opt_join_seg = value != 0;
-  // (environment overrides exist in DEVELOPMENT builds only - RDM_DEV_VARIANTS=1, in-process A/B runs of bench.py; the shipped library reads no
-  // environment: an option is what the caller set.  Thresholds are clamped to what layout() sized the pack buffers for.)
-  else if (option == RDM_NET_OPT_SPLIT_BWD) {
-    n->opt_split_bwd = value != 0;
-#ifdef RDM_DEV_VARIANTS
-    if (getenv("RDM_XS_MIN_PIXELS")) n->xs_min_pixels = std::max(XS_LAYOUT_MIN_PIXELS, atoi(getenv("RDM_XS_MIN_PIXELS")));
-    if (getenv("RDM_XS_WG3_MIN")) n->xs_wg3_min_pixels = std::max(XS_LAYOUT_MIN_PIXELS, atoi(getenv("RDM_XS_WG3_MIN")));
-#endif
-  }
-  else if (option == RDM_NET_OPT_PREPACK) {
-    n->opt_prepack = value != 0;
-#ifdef RDM_DEV_VARIANTS
-    if (getenv("RDM_PREPACK")) n->opt_prepack = atoi(getenv("RDM_PREPACK")) != 0;
-#endif
-  }
-  else if (option == RDM_NET_OPT_DEFER_NORM1) {
-    n->opt_defer_norm1 = value != 0;
-#ifdef RDM_DEV_VARIANTS
-    if (getenv("RDM_DEFER_NORM1")) n->opt_defer_norm1 = atoi(getenv("RDM_DEFER_NORM1")) != 0;
-#endif
-  }
+  else if (option == RDM_NET_OPT_SPLIT_BWD) n->opt_split_bwd = value != 0;
+  else if (option == RDM_NET_OPT_PREPACK) n->opt_prepack = value != 0;
+  else if (option == RDM_NET_OPT_DEFER_NORM1) n->opt_defer_norm1 = value != 0;
   else if (option == RDM_NET_OPT_GEMM_BF16) n->opt_gemm_bf16 = value == 1 ? 3 : value == 2 ? 1 : value == 3 ? 2 : 0;      // 1 = both, 2 = forward GEMMs only, 3 = gradient GEMMs only
   else if (option == RDM_NET_OPT_SPLIT_ROWS) n->opt_split_rows = value != 0;
   else if (option == RDM_NET_OPT_WINO_X6) n->opt_wino_x6 = value != 0;
   else if (option == RDM_NET_OPT_FUSE_STATS3) n->opt_fuse_stats3 = value != 0;
-  else if (option == RDM_NET_OPT_SPLIT_FWD) {
-    n->opt_split_fwd = value != 0;
-#ifdef RDM_DEV_VARIANTS
-    if (getenv("RDM_XF_MIN_PIXELS")) n->xf_min_pixels = std::max(XF_LAYOUT_MIN_PIXELS, atoi(getenv("RDM_XF_MIN_PIXELS")));
-#endif
-  }
+  else if (option == RDM_NET_OPT_SPLIT_FWD) n->opt_split_fwd = value != 0;
   else { set_error("rdm_net_set_option: unknown option %d", option); return RDM_ERR_BAD_ARGUMENT; }
   if (option != RDM_NET_OPT_JOIN_PER_SEGMENT) n->routes_valid = false;       // (set before every backward; it routes nothing)
   return RDM_OK;

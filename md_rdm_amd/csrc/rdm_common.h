@@ -40,15 +40,6 @@ extern long long g_launches;
     }                                                                                 \
   } while (0)
 
-// Development A/B switch behind rdm_debug_variant (the measured alternatives DESIGN.md cites).  It exists only in builds made with
-// RDM_DEV_VARIANTS=1 (`RDM_DEV_VARIANTS=1 python -m md_rdm_amd.build`); in the shipped library it is the constant 0, every
-// `g_variant == N` branch folds away at compile time and no launcher reads mutable process-wide state.
-#ifdef RDM_DEV_VARIANTS
-extern int g_variant;
-#else
-constexpr int g_variant = 0;
-#endif
-
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Deterministic reduction mode (rdm_net_set_option RDM_NET_OPT_DETERMINISTIC; tests): while a plan call that asked for it is running on
@@ -93,7 +84,7 @@ struct FwdArgs {            // C[m][n] = sum_{tap,c} f(A[pix(m,tap)][c]) * Wt[ta
   double* stat0; double* stat1;               // STORE_STATS: sum v, sum v^2;  MASK_STATS: sum dz, sum dz*x
   const float* X; int ldx; const float* x_scale; const float* x_shift;  // MASK_STATS: forward pre-BN value + its affine
   int split_k;                                // >1 => EPI_ATOMIC into pre-zeroed out
-  int xcd_flat;                               // 1: keep the hardware block order (A/B switch; default 0 = XCD-aware order)
+  int xcd_flat;                               // 1: keep the hardware block order (single column tile); 0 = XCD-aware order; 8 = row-grouped order
   int add_out;                                // EPI_STORE_STATS: out = out + v (the statistics are taken of the SUM): completes a K-partial
   int accumulate;                             // 1: add into `out` (f32 atomics), never zero it - the caller owns the initial value
   unsigned a_bytes, w_bytes;                  // set by the launcher: addressable extents of A / Wt (buffer descriptors)
@@ -135,7 +126,7 @@ struct WgradArgs {          // dW[tap][n][c] += sum_m G[m][n] * f(Xs[pix(m,tap)]
   int split_k;
   long n_items;                               // set by the launcher: column tiles x row tiles x splits
   unsigned g_bytes, x_bytes;                  // set by the launcher: addressable extents of G / Xs
-  int xcd_flat;                               // 1: keep the hardware block order (A/B switch)
+  int xcd_flat;                               // vestigial: always 0 = XCD-aware order (1 kept the hardware block order; only the removed A/B switch set it)
   int xsplit;                                 // launch_xs_wgrad1x1 / launch_xs_wgrad3x3 (xsplit.h) only: 3 (or any value but 1) = split precision, three bf16 MFMAs
                                               // per product; 1 = operands rounded to bf16, one MFMA (the mixed-precision mode).  launch_conv_wgrad takes 0 only
   int g_bf16;                                 // xsplit == 1 only: G is rows of bf16 (ldg in elements of that type)

@@ -111,9 +111,7 @@ struct WinoFwdArgs {
 // for slab s+1 while slab s is being multiplied).  The two streams meet at ONE workgroup barrier per slab; the producers' gathers for
 // slab s+2 are issued before it and have a whole slab time to land.  (A first version in which all 8 waves did both jobs in lockstep
 // ran at 54 % of the matrix pipe: both waves of a SIMD stalled on the same loads at the same time.)
-// ABL: timing-only ablations for tools/wino_bench.py (RDM_DEV_VARIANTS builds; results are wrong): 1 no gathers after the prologue,
-// 2 no weight-fragment loads in the loop, 4 no MFMAs, 8 no producer arithmetic (BatchNorm, transforms)
-template <bool BNRELU, int ABL = 0>
+template <bool BNRELU>
 __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p) {
   __shared__ __attribute__((aligned(1024))) float smem[2 * 16 * TT * 16];        // V double buffer: 2 x 64 KB; reused by the epilogue
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p)
         }
       };
       auto transform_store = [&](int s, float* Vb) {
-        if (BNRELU && !(ABL & 8)) {
+        if (BNRELU) {
           const f32x4 sc = *reinterpret_cast<const f32x4*>(p.a_scale + s * 16 + cq * 4), sh = *reinterpret_cast<const f32x4*>(p.a_shift + s * 16 + cq * 4);
 #pragma unroll
           for (int c = 0; c < 4; ++c)
@@ -187,14 +185,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p)
 #define RDM_WINO_1D(v, i0, i1, i2, i3)                                                        \
         { const float d0 = v[i0], d1 = v[i1], d2 = v[i2], d3 = v[i3];                         \
           v[i0] = d0 - d2; v[i1] = d1 + d2; v[i2] = d2 - d1; v[i3] = d1 - d3; }
-        if (!(ABL & 8)) {
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
+        for (int c = 0; c < 4; ++c) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) RDM_WINO_1D(rv[c], j, 4 + j, 8 + j, 12 + j)                      // B^T d: columns
+          for (int j = 0; j < 4; ++j) RDM_WINO_1D(rv[c], j, 4 + j, 8 + j, 12 + j)                      // B^T d: columns
 #pragma unroll
-            for (int i = 0; i < 4; ++i) RDM_WINO_1D(rv[c], 4 * i, 4 * i + 1, 4 * i + 2, 4 * i + 3)      // (.) B: rows
-          }
+          for (int i = 0; i < 4; ++i) RDM_WINO_1D(rv[c], 4 * i, 4 * i + 1, 4 * i + 2, 4 * i + 3)      // (.) B: rows
         }
 #undef RDM_WINO_1D
 #pragma unroll
@@ -210,7 +206,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p)
         const int buf = (s - s_begin) & 1;
         if (s + 1 < s_end) {
           transform_store(s + 1, smem + (buf ^ 1) * (16 * TT * 16));      // raw(s+1) has been in flight for a whole slab time
-          if (!(ABL & 1)) load_raw(min(s + 2, s_end - 1));
+          load_raw(min(s + 2, s_end - 1));
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the LDS stores have landed before the barrier releases the readers
         }
         __builtin_amdgcn_s_barrier();
@@ -237,10 +233,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p)
         aq[0] = load_a1(Vb, pos0, 0);
 #pragma unroll
         for (int pp = 0; pp < 4; ++pp) {
-          if (!(ABL & 2)) {
-            if (pp < 3) load_b(s, pos0 + pp + 1, bq[(pp + 1) & 1]);
-            else load_b(min(s + 1, s_end - 1), pos0, bq[0]);
-          } else if (s == s_begin) load_b(s, pos0 + pp, bq[(pp + 1) & 1]);
+          if (pp < 3) load_b(s, pos0 + pp + 1, bq[(pp + 1) & 1]);
+          else load_b(min(s + 1, s_end - 1), pos0, bq[0]);
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt) {
             const int cur = (pp * 4 + mt) & 1;
@@ -251,8 +245,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p)
             for (int e = 0; e < 4; ++e)
 #pragma unroll
               for (int nt = 0; nt < 3; ++nt)
-                if (!(ABL & 4)) acc[pp][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[cur][e], bq[pp & 1][nt][e], acc[pp][mt][nt], 0, 0, 0);
-                else asm volatile("" :: "v"(aq[cur][e]), "v"(bq[pp & 1][nt][e]));
+                acc[pp][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[cur][e], bq[pp & 1][nt][e], acc[pp][mt][nt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
@@ -436,17 +429,10 @@ struct WinoX6Args {
   const unsigned char* U;
   float* out; int ldc; int N;
   int B, H, W, TH, TW, T;
-  int split;
-  int abl;                 // development builds only: timing-only ablations (RDM_WX6_ABL; results wrong by construction): 1 every gather of a thread from one pixel,
-                           // 2 no weight loads in the loop, 4 no MFMAs, 8 no split, 16 no LDS stores (profiles/r05_wino_x6_ablation.txt)
   unsigned a_bytes, u_bytes;
+  int split;              // after the extents: with `split` before them the kernel's prologue and code size change (+1 SGPR, +44 B) and the x6 step measured 0.1-0.3 ms slower
 };
 
-#ifdef RDM_DEV_VARIANTS
-#define WX6_ABL(bit) (p.abl & (bit))
-#else
-#define WX6_ABL(bit) false
-#endif
 template <bool BNRELU>
 __global__ __launch_bounds__(448, 2) void conv3x3_wino_x6_kernel(WinoX6Args p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char wx_smem[];      // V double buffer: 2 x XIMG; reused by the epilogue
@@ -492,10 +478,6 @@ __global__ __launch_bounds__(448, 2) void conv3x3_wino_x6_kernel(WinoX6Args p) {
             voff[i * 4 + j] = ok ? (unsigned)((b * p.H + y) * p.W + x) * (unsigned)(p.lda * 4) + (unsigned)(cq * 16) : WOOB;
             hi[i * 4 + j] = ok ? __builtin_inff() : 0.f;
           }
-        if (WX6_ABL(1)) {
-#pragma unroll
-          for (int q = 0; q < 16; ++q) voff[q] = voff[5];
-        }
       }
       const __amdgpu_buffer_rsrc_t srdA = wsrd(p.A, p.a_bytes);
       const unsigned rowoff = (unsigned)(tl * XROW + cq * 8);
@@ -531,14 +513,11 @@ __global__ __launch_bounds__(448, 2) void conv3x3_wino_x6_kernel(WinoX6Args p) {
 #pragma unroll
           for (int pos = 0; pos < 16; ++pos) {
             u32x2 p0, p1, p2;
-            if (WX6_ABL(8)) { p0 = u32x2{__float_as_uint(rv[0][pos]), __float_as_uint(rv[1][pos])}; p1 = u32x2{__float_as_uint(rv[2][pos]), __float_as_uint(rv[3][pos])}; p2 = p0; }
-            else wsplit3x4(rv[0][pos], rv[1][pos], rv[2][pos], rv[3][pos], p0, p1, p2);
+            wsplit3x4(rv[0][pos], rv[1][pos], rv[2][pos], rv[3][pos], p0, p1, p2);
             unsigned char* row = Vb + pos * (TX * XROW) + rowoff;
-            if (!WX6_ABL(16)) {
             *reinterpret_cast<u32x2*>(row) = p0;
             *reinterpret_cast<u32x2*>(row + 32) = p1;
             *reinterpret_cast<u32x2*>(row + 64) = p2;
-            } else asm volatile("" :: "v"(p0), "v"(p1), "v"(p2));
           }
         }
       };
@@ -600,7 +579,7 @@ __global__ __launch_bounds__(448, 2) void conv3x3_wino_x6_kernel(WinoX6Args p) {
           if (q < total) {                                           // (wave-uniform)
             const int pp = u & 3;
             const unsigned char* Vb = wx_smem + ((q >> 2) & 1) * XIMG;
-            if (q + 2 < total && !WX6_ABL(2)) load_b(s_begin + ((q + 2) >> 2), pos0 + ((u + 2) & 3), bq[(u + 2) % 3]);
+            if (q + 2 < total) load_b(s_begin + ((q + 2) >> 2), pos0 + ((u + 2) & 3), bq[(u + 2) % 3]);
             if (pp == 0) load_a(Vb, pos0, 0, aq[0]);
 #pragma unroll
             for (int mt = 0; mt < 3; ++mt) {
@@ -610,7 +589,6 @@ __global__ __launch_bounds__(448, 2) void conv3x3_wino_x6_kernel(WinoX6Args p) {
               __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
               for (int nt = 0; nt < 3; ++nt) {                       // small terms first
-                if (WX6_ABL(4)) { asm volatile("" :: "v"(aq[cur][0]), "v"(aq[cur][1]), "v"(aq[cur][2]), "v"(bq[u % 3][nt][0]), "v"(bq[u % 3][nt][1])); continue; }
                 acc[pp][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[cur][2], bq[u % 3][nt][1], acc[pp][mt][nt], 0, 0, 0);      // v2 u0 + v0 u2
                 acc[pp][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[cur][1], bq[u % 3][nt][0], acc[pp][mt][nt], 0, 0, 0);      // v1 u0 + v1 u1
                 acc[pp][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[cur][0], bq[u % 3][nt][0], acc[pp][mt][nt], 0, 0, 0);      // v0 u0 + v0 u1
@@ -1015,10 +993,6 @@ int launch_conv3x3_wino_fwd(const WinoConv& a, hipStream_t s) {
     k.A = a.A; k.lda = a.lda; k.C = a.C; k.a_scale = a.a_scale; k.a_shift = a.a_shift; k.U = reinterpret_cast<const unsigned char*>(a.U);
     k.out = split > 1 ? a.partial : a.out; k.ldc = a.ldc; k.N = a.N;
     k.B = a.B; k.H = a.H; k.W = a.W; k.TH = TH; k.TW = TW; k.T = T; k.split = split; k.a_bytes = (unsigned)ab; k.u_bytes = (unsigned)wino_u_bytes(a.C, true);
-#ifdef RDM_DEV_VARIANTS
-    static const int abl_env = getenv("RDM_WX6_ABL") ? atoi(getenv("RDM_WX6_ABL")) : 0;
-    k.abl = abl_env;
-#endif
     void* prof = profile_begin(s, 2.0 * M * a.N * 9.0 * a.C, 18);
     RDM_CENSUS("conv3x3_wino_x6_kernel/%s/%s", a.a_scale ? "bn1" : "bn0", split > 1 ? "PARTIAL" : (a.stat0 ? "STORE+stats" : "STORE"));
     dim3 grid((unsigned)cdiv(T, TX), (unsigned)split);
@@ -1040,13 +1014,6 @@ int launch_conv3x3_wino_fwd(const WinoConv& a, hipStream_t s) {
   void* prof = profile_begin(s, 2.0 * M * a.N * 9.0 * a.C, 9);
   RDM_CENSUS("conv3x3_wino_fwd_kernel/%s/%s", a.a_scale ? "bn1" : "bn0", split > 1 ? "PARTIAL" : (a.stat0 ? "STORE+stats" : "STORE"));
   dim3 grid((unsigned)cdiv(T, TT), (unsigned)split);
-#ifdef RDM_DEV_VARIANTS
-  const char* abl_env = getenv("RDM_WINO_ABL");
-  const int abl = abl_env ? atoi(abl_env) : 0;
-#define RDM_ABL(N_) if (abl == N_) hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<true, N_>), grid, dim3(512), 0, s, k); else
-  RDM_ABL(1) RDM_ABL(2) RDM_ABL(3) RDM_ABL(4) RDM_ABL(8) RDM_ABL(9) RDM_ABL(11) RDM_ABL(12) RDM_ABL(13) RDM_ABL(15)
-#undef RDM_ABL
-#endif
   if (a.a_scale) hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<true>), grid, dim3(512), 0, s, k);
   else hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<false>), grid, dim3(512), 0, s, k);
   profile_end(prof, s);

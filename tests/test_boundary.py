@@ -52,6 +52,25 @@ def test_bench_library_is_separate_from_the_product(L):
     assert "microbench" not in open(HEADER).read()
 
 
+def test_library_reads_no_environment_and_has_no_variant_switch(L):
+    """DESIGN 1, "State after init": the library reads no environment and has no process-wide A/B state.  It imports none of the
+    environment readers, exports no rdm_debug_variant, and the name survives only as a Python stub that accepts 0 (bench.py passes
+    RDM_VARIANT through it)."""
+    import subprocess
+    from md_rdm_amd import _lib
+
+    def dynsyms(which):
+        out = subprocess.run(["nm", "-D", which, _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+        return {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
+    undefined, defined = dynsyms("--undefined-only"), dynsyms("--defined-only")
+    assert "hipLaunchKernel" in undefined and "rdm_version" in defined          # the listing is read correctly
+    assert not undefined & {"getenv", "secure_getenv", "atoi"}
+    assert "rdm_debug_variant" not in defined
+    assert L.rdm_debug_variant(0) is None
+    with pytest.raises(_lib.RdmError, match="removed"):
+        L.rdm_debug_variant(7)
+
+
 def test_every_entry_point_cites_the_reference():
     hdr = open(HEADER).read()
     assert hdr.count("RDM_Net.py:") >= 6 and hdr.count("computations.py:") >= 8

@@ -1,9 +1,8 @@
-"""In-process A/B microbenchmark of the conv kernels through the C ABI (the numbers DESIGN.md 4.1 quotes).
+"""Microbenchmark of the conv kernels through the C ABI (the numbers DESIGN.md 4.1 quotes).
 
-    SHAPE=B,H,W,Cb CIN=c VARIANTS=0,9 python tools/conv_microbench.py {fwd1|dg1|wg1|fwd3|dg3|wg3|all} [reps]
+    SHAPE=B,H,W,Cb CIN=c python tools/conv_microbench.py {fwd1|dg1|wg1|fwd3|dg3|wg3|all} [reps]
 
-SHAPE defaults to the dense_e2 geometry (16,57,76,2736), CIN to 336; VARIANTS are rdm_debug_variant values timed alternately
-in one process (box-to-box variance is 5-10 %, so only in-process comparisons are meaningful)."""
+SHAPE defaults to the dense_e2 geometry (16,57,76,2736), CIN to 336 (box-to-box variance is 5-10 %: compare within one process only)."""
 import ctypes as C, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -43,17 +42,13 @@ def wg3n(): check(L.rdm_conv2d_wgrad(C.byref(d3), ptr(g48), ptr(Y), None, None, 
 def fwd1n(): check(L.rdm_conv2d_fwd(C.byref(d1), ptr(X), ptr(w1), None, None, None, ptr(dZ), ptr(s0), ptr(s1), stream()))
 def wg1n(): check(L.rdm_conv2d_wgrad(C.byref(d1), ptr(dZ), ptr(X), None, None, ptr(dW1), stream()))
 ops = {"fwd3_nobn": (fwd3n, 2*M*48*Cb*9), "wg3_nobn": (wg3n, 2*M*48*Cb*9), "fwd1_nobn": (fwd1n, 2*M*Cb*CIN), "wg1_nobn": (wg1n, 2*M*Cb*CIN), "fwd3": (fwd3, 2*M*48*Cb*9), "wg3": (wg3, 2*M*48*Cb*9), "dg3": (dg3, 2*M*48*Cb*9), "fwd1": (fwd1, 2*M*Cb*CIN), "wg1": (wg1, 2*M*Cb*CIN), "dg1": (dg1, 2*M*Cb*CIN)}
-variants = [int(v) for v in os.environ.get("VARIANTS", "0").split(",")]
 for name, (fn, fl) in ops.items():
     if which != "all" and which != name: continue
-    res = {v: [] for v in variants}
+    res = []
     for rnd in range(4):
-        for v in variants:
-            L.rdm_debug_variant(v)
-            fn(); torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(reps): fn()
-            torch.cuda.synchronize()
-            res[v].append((time.perf_counter() - t0) / reps)
-    L.rdm_debug_variant(0)
-    print(name + ": " + "  ".join(f"v{v}: {min(r)*1e3:.3f} ms {fl/min(r)/1e12:.1f} TF ({fl/min(r)/1e12/157.3*100:.0f}%)" for v, r in res.items()), flush=True)
+        fn(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps): fn()
+        torch.cuda.synchronize()
+        res.append((time.perf_counter() - t0) / reps)
+    print(f"{name}: {min(res)*1e3:.3f} ms {fl/min(res)/1e12:.1f} TF ({fl/min(res)/1e12/157.3*100:.0f}%)", flush=True)

@@ -5,7 +5,6 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from md_rdm_amd import _lib
 L = _lib.lib()
-if os.environ.get("RDM_VARIANT"): L.rdm_debug_variant(int(os.environ["RDM_VARIANT"]))
 dev = torch.device("cuda:0")
 B, H, W, Cb = 16, 57, 76, 2736
 M = B * H * W
