@@ -169,6 +169,13 @@ _VIZ_SIGNATURES = {
     "rdm_viz_rows_u8": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, f64, f64, vp, i32, vp]),
 }
 
+# include/rdm_eval.h: standard-protocol evaluation, part of librdm_hip.so, declared in a header of its own
+_EVAL_SIGNATURES = {
+    "rdm_eval_standard_workspace_bytes": (sz, [i32, i32, i32]),
+    "rdm_eval_standard_f64": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, f64, f64, C.POINTER(i32), vp, vp, vp, sz, vp]),
+}
+EVAL_ALIGN = {"none": 0, "median": 1, "logmean": 2}          # RDM_EVAL_ALIGN_* (include/rdm_eval.h)
+
 _lib = None
 _bench = None
 
@@ -190,7 +197,7 @@ def lib():
             raise RdmError(f"{LIB_PATH} not found - run `python -m md_rdm_amd.build` (hipcc --offload-arch=gfx950). "
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _VIZ_SIGNATURES):
+        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -235,6 +242,10 @@ def bench_symbols():
 
 def viz_symbols():
     return list(_VIZ_SIGNATURES)
+
+
+def eval_symbols():
+    return list(_EVAL_SIGNATURES)
 
 
 def check(rc):

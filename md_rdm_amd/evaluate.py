@@ -13,6 +13,17 @@ are the means over the samples of the per-sample values - what the reference's b
 samples r, r + world, ... (no sample is dropped; the shards may differ in size) and the ranks all-reduce the per-metric sums and the sample
 count once at the end; rank 0 prints and writes the result.  ``--rows DIR`` also writes ``row_IIIII.png`` (I = the sample's index) for the first
 ``--rows_max`` samples of each rank: input | normalised target | the map the metrics saw, the two maps over one colour range (md_rdm_amd.viz).
+
+``--protocol standard`` scores the way the published tables do instead (``metrics.StandardMetrics``, include/rdm_eval.h): linear depth exp(map)
+resized to the resolution of the depth the loader returns, valid pixels only (finite, inside (--min_depth, --max_depth) and --crop), a per-image scale
+alignment (--align), the aligned prediction clamped to the depth range, and the Eigen et al. error set per image, averaged over the images.
+Its figures are NOT comparable with the reference protocol's: ``rmse`` there is the true root mean square, and the deltas are taken of aligned
+linear depth.  Images without a valid pixel are left out and counted as ``skipped``.  The rows then show input | raw depth | aligned prediction.
+NB the command scores at the LOADER's output size (--size, 226x226 by default: the depth after the split's Resize + CenterCrop), and --crop is in
+that frame's coordinates.  Its figures are therefore not yet the 480x640 Eigen-crop numbers of the published NYU tables; the kernel and
+``harness.evaluate`` take depth of any size, so batches that carry the depth at its native resolution are scored there.
+
+  python -m md_rdm_amd.evaluate --checkpoint last.ckpt --nyu_path /data/nyudepthv2 --split test --protocol standard --crop 8 8 218 218 --out results.json
 """
 import json
 import os
@@ -39,6 +50,12 @@ def build_parser():
     p.add_argument("--metrics", default=list(DEFAULT_METRICS), nargs="+")
     p.add_argument("--exp_pred", action="store_true", help="compare exp(map) with the target instead of the log-domain map: this DEPARTS from the reference, "
                    "which compares the recombination as it is (module.py:117)")
+    p.add_argument("--protocol", type=str, default="reference", choices=["reference", "standard"], help="reference: the reference's validation (log-domain map "
+                   "against the normalised 128x128 target); standard: aligned full-resolution linear depth, the Eigen et al. error set")
+    p.add_argument("--align", type=str, default="median", choices=["none", "median", "logmean"], help="standard protocol: per-image scale alignment")
+    p.add_argument("--min_depth", type=float, default=1e-3, help="standard protocol: valid pixels have min_depth < d < max_depth; the prediction is clamped to the range")
+    p.add_argument("--max_depth", type=float, default=10.0)
+    p.add_argument("--crop", type=int, nargs=4, default=None, metavar=("Y0", "X0", "Y1", "X1"), help="standard protocol: score rows [Y0, Y1) and columns [X0, X1) only")
     p.add_argument("--out", type=str, default=None, help="write the result as JSON here")
     p.add_argument("--worker", default=6, type=int, help="threads that decode raw samples (--nyu_path)")
     p.add_argument("--rows", type=str, default=None, metavar="DIR", help="write input | normalised target | prediction PNG rows here")
@@ -57,6 +74,25 @@ def synthetic_samples(n, h, w):
     return np.ascontiguousarray(np.broadcast_to(x, (n,) + x.shape[1:])), y
 
 
+def make_computer(args):
+    """the metric computer the flags ask for; every refusal is a SystemExit before anything touches a GPU"""
+    from .metrics import MetricComputation, StandardMetrics
+    try:
+        if args.protocol == "reference":
+            return MetricComputation(args.metrics)
+        if args.exp_pred:
+            raise SystemExit("md_rdm_amd.evaluate: --exp_pred belongs to --protocol reference; the standard protocol always compares linear depth")
+        names = None if list(args.metrics) == DEFAULT_METRICS else args.metrics          # --metrics left alone: the standard list
+        H, W = args.size
+        if args.crop is not None and not (0 <= args.crop[0] < args.crop[2] <= H and 0 <= args.crop[1] < args.crop[3] <= W):
+            raise SystemExit("md_rdm_amd.evaluate: --crop %s is empty or outside the %dx%d frame" % (" ".join(map(str, args.crop)), H, W))
+        return StandardMetrics(names, align=args.align, min_depth=args.min_depth, max_depth=args.max_depth, crop=args.crop)
+    except KeyError as e:
+        raise SystemExit("md_rdm_amd.evaluate: %s" % e.args[0])
+    except ValueError as e:
+        raise SystemExit("md_rdm_amd.evaluate: %s" % e)
+
+
 def shard(indices, rank, world):
     """rank r of `world` takes indices[r::world]: every sample exactly once, shards of unequal size allowed"""
     return list(indices)[rank::world]
@@ -72,6 +108,7 @@ def main(argv=None):
         raise SystemExit("md_rdm_amd.evaluate: --synthetic must be positive")
     if args.rows_max < 0:
         raise SystemExit("md_rdm_amd.evaluate: --rows_max must not be negative")
+    computer = make_computer(args)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit(NO_GPU)
@@ -85,12 +122,7 @@ def main(argv=None):
         dist.init_process_group("nccl", device_id=dev)
 
     from . import checkpoint, filler, harness
-    from .metrics import MetricComputation
     from .network.RDM_Net import DepthEstimationNet
-    try:
-        computer = MetricComputation(args.metrics)
-    except KeyError as e:
-        raise SystemExit("md_rdm_amd.evaluate: %s" % e.args[0])
     model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
     if args.checkpoint:
         checkpoint.from_lightning(model, args.checkpoint)
@@ -132,10 +164,16 @@ def main(argv=None):
         for name in computer.names:
             print("%s %.6f" % (name, result[name]), flush=True)
         print("n %d" % result["n"], flush=True)
+        standard = args.protocol == "standard"
+        if standard:
+            print("skipped %d" % result["skipped"], flush=True)
         if args.out:
             record = {"split": source, "n": result["n"], "batch_size": args.batch_size, "precision": args.precision, "size": [H, W], "exp_pred": bool(args.exp_pred),
                       "relative_decoders": list(args.relative_decoders), "checkpoint": args.checkpoint, "world": world,
-                      "metrics": {name: result[name] for name in computer.names}}
+                      "metrics": {name: result[name] for name in computer.names}, "protocol": args.protocol}
+            if standard:
+                record.update(align=args.align, min_depth=args.min_depth, max_depth=args.max_depth, crop=list(args.crop) if args.crop else None,
+                              skipped=result["skipped"])
             d = os.path.dirname(os.path.abspath(args.out))
             os.makedirs(d, exist_ok=True)
             with open(args.out, "w") as fh:

@@ -80,38 +80,57 @@ def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_ou
     ``exp_pred``: compare exp(map) - not what the reference does.  ``return_maps``: also return the (n,1,128,128) maps of this rank.
     ``rows_out``: a list that receives, for the first ``rows_max`` samples of this rank, the (H,3W,3) uint8 host image input | normalised target
     (``compute_rows``' target_out) | the map the metrics saw (exp of it under ``exp_pred``), rendered on the device in one launch per batch
-    (viz.comparison_rows) and copied over once per batch."""
+    (viz.comparison_rows) and copied over once per batch.
+    ``metrics`` may also be a ``metrics.StandardMetrics``: the standard protocol (linear depth at the depth's own resolution, valid pixels, scale
+    alignment, the Eigen et al. error set; include/rdm_eval.h), again ``predict`` + ONE launch per batch with the rows kept on the device.  The
+    result is the mean over the samples of the per-sample values (the per-image averaging of the NYU / KITTI protocols); samples without a
+    valid pixel are left out of the means and counted in ``"skipped"``; if every sample is skipped it raises.  ``rows_out`` then shows
+    input | raw depth | the aligned, clamped prediction over one colour range.  ``exp_pred`` does not apply."""
     import torch.distributed as dist
-    from .metrics import MetricComputation, mean_over_shards
-    mc = metrics if isinstance(metrics, MetricComputation) else MetricComputation(list(metrics))
+    from .metrics import MetricComputation, StandardMetrics, mean_over_shards
+    standard = isinstance(metrics, StandardMetrics)
+    if standard and exp_pred:
+        raise ValueError("evaluate: exp_pred belongs to the reference protocol; the standard protocol always compares linear depth")
+    mc = metrics if isinstance(metrics, (MetricComputation, StandardMetrics)) else MetricComputation(list(metrics))
     rows, maps = [], []
     for x, y in batches:
         pred = model.predict(x)
         want = rows_out is not None and len(rows_out) < rows_max
-        tgt = torch.empty_like(pred) if want else None
-        rows.append(mc.compute_rows(pred, y, exp_pred=exp_pred, target_out=tgt))
+        if standard:
+            tgt = torch.empty(y.shape, dtype=torch.float64, device=pred.device) if want else None      # q, at the depth's resolution
+            rows.append(mc.compute_rows(pred, y, pred_out=tgt))
+        else:
+            tgt = torch.empty_like(pred) if want else None
+            rows.append(mc.compute_rows(pred, y, exp_pred=exp_pred, target_out=tgt))
         if want:
             from . import viz
             k = min(x.shape[0], rows_max - len(rows_out))
-            img = viz.comparison_rows(x[:k].float(), tgt[:k], (pred.exp() if exp_pred else pred)[:k])
+            if standard:
+                img = viz.comparison_rows(x[:k].float(), y[:k], tgt[:k])
+            else:
+                img = viz.comparison_rows(x[:k].float(), tgt[:k], (pred.exp() if exp_pred else pred)[:k])
             rows_out.extend(img.cpu().numpy())
         if return_maps:
             maps.append(pred)
     values = mc.values_from_rows(torch.cat(rows).cpu()) if rows else []          # the one device-to-host copy
+    skipped = sum(1 for v in values if v is None)                                # standard protocol: samples without a valid pixel
+    values = [v for v in values if v is not None]
     sums = [0.0] * len(mc.names)
     for v in values:                                                             # per-sample values summed in order, as MetricComputation.compute does
         for i, s in enumerate(v):
             sums[i] += s
     n = len(values)
     if dist.is_initialized() and dist.get_world_size() > 1:
-        t = torch.tensor(sums + [float(n)], dtype=torch.float64, device=next(model.parameters()).device)
+        t = torch.tensor(sums + [float(n), float(skipped)], dtype=torch.float64, device=next(model.parameters()).device)
         dist.all_reduce(t)
         t = t.cpu()
-        sums, n = [float(s) for s in t[:-1]], int(t[-1])
+        sums, n, skipped = [float(s) for s in t[:-2]], int(t[-2]), int(t[-1])
     if n == 0:
-        raise ValueError("evaluate: no samples")
+        raise ValueError("evaluate: no samples" if not skipped else "evaluate: none of the %d samples has a valid pixel" % skipped)
     means, n = mean_over_shards([(sums, n)])
     result = dict(zip(mc.names, means), n=n)
+    if standard:
+        result["skipped"] = skipped
     return (result, torch.cat(maps)) if return_maps else result
 
 

@@ -92,6 +92,87 @@ class MetricComputation:
         return self.sum[self.names.index(metric)] / self.count
 
 
+# the standard protocol (include/rdm_eval.h): name -> how the value is formed from a row of rdm_eval_standard_f64
+_STANDARD = ("delta1", "delta2", "delta3", "abs_rel", "sq_rel", "rmse", "rmse_log", "silog", "log10", "mae", "scale")
+STANDARD_COLS = 16
+
+
+class StandardMetrics:
+    """The evaluation protocol of the published depth-estimation tables (Eigen et al.), beside the reference's (``MetricComputation``): linear
+    depth ``exp(map)`` at the ground truth's OWN resolution, valid pixels only (finite, ``min_depth < d < max_depth``, inside ``crop`` =
+    (y0, x0, y1, x1) when given), a per-image scale ``align``-ment (``"median"``: median(d) / median(p); ``"logmean"``: exp(mean ln d - mean ln p);
+    ``"none"``), the aligned prediction clamped to [min_depth, max_depth], then per image
+
+      delta1..3  share of pixels with max(q/d, d/q) < 1.25^k (a float64 quotient)     abs_rel  mean |q-d|/d          sq_rel  mean (q-d)^2/d
+      rmse       sqrt(mean (q-d)^2)                                                  rmse_log sqrt(mean (ln q - ln d)^2)
+      silog      100 sqrt(max(mean g^2 - (mean g)^2, 0)), g = ln q - ln d            log10    mean |log10 q - log10 d|   mae  mean |q-d|
+      scale      the alignment scale s
+
+    NB ``rmse`` here is the TRUE root mean square.  It is not the reference's metric of the same name (``MetricComputation``'s 'rmse' is the
+    reference's mean sqrt((p-t)^2/t), metrics.py:107-110), and none of these figures is comparable with the reference protocol's.
+    ``compute_rows`` is one launch per batch (``rdm_eval_standard_f64``); ``values_from_rows`` forms the values on the host."""
+
+    available = _STANDARD
+
+    def __init__(self, names=None, align="median", min_depth=1e-3, max_depth=10.0, crop=None):
+        names = list(_STANDARD) if names is None else list(names)
+        for m in names:
+            if m not in _STANDARD:
+                raise KeyError(f"metric '{m}' is not built in the standard protocol (available: {sorted(_STANDARD)})")
+        if align not in _lib.EVAL_ALIGN:
+            raise ValueError(f"align '{align}' is not one of {sorted(_lib.EVAL_ALIGN)}")
+        if not (0 <= float(min_depth) < float(max_depth)):
+            raise ValueError(f"need 0 <= min_depth < max_depth, got {min_depth}, {max_depth}")
+        if crop is not None:
+            crop = tuple(int(c) for c in crop)
+            if len(crop) != 4 or not (0 <= crop[0] < crop[2] and 0 <= crop[1] < crop[3]):
+                raise ValueError(f"crop must be (y0, x0, y1, x1) with 0 <= y0 < y1 and 0 <= x0 < x1, got {crop}")
+        self.names, self.align, self.min_depth, self.max_depth, self.crop = names, align, float(min_depth), float(max_depth), crop
+
+    def compute_rows(self, pred, depth, pred_out=None):
+        """The (B,1,128,128) float64 log map ``predict`` returns and the loader's raw (B,1,H,W) float32 / float64 depth -> the (B,16) float64
+        DEVICE tensor of per-sample sums (columns: include/rdm_eval.h).  One launch, nothing is copied to the host and nothing synchronises.
+        ``pred_out`` (B,1,H,W) float64: optionally receives the aligned, clamped prediction at every pixel."""
+        import ctypes as C
+        if not pred.is_cuda or not depth.is_cuda:
+            raise _lib.RdmError("metrics run on the GPU only")
+        if pred.dim() != 4 or tuple(pred.shape[1:]) != (1, 128, 128) or pred.dtype != torch.float64:
+            raise _lib.RdmError("compute_rows: pred must be the (B,1,128,128) float64 map of DepthEstimationNet.predict, got %s %s" % (pred.dtype, tuple(pred.shape)))
+        if depth.dim() != 4 or depth.shape[0] != pred.shape[0] or depth.shape[1] != 1 or depth.dtype not in (torch.float32, torch.float64):
+            raise _lib.RdmError("compute_rows: depth must be (B,1,H,W) float32 or float64 with pred's B, got %s %s" % (depth.dtype, tuple(depth.shape)))
+        if pred_out is not None and (pred_out.dtype != torch.float64 or tuple(pred_out.shape) != tuple(depth.shape) or not pred_out.is_cuda):
+            raise _lib.RdmError("compute_rows: pred_out must be a float64 device tensor of depth's shape, got %s %s" % (pred_out.dtype, tuple(pred_out.shape)))
+        B, _, H, W = depth.shape
+        p, d = pred.detach().contiguous(), depth.detach().contiguous()
+        L = _lib.lib()
+        need = L.rdm_eval_standard_workspace_bytes(B, H, W)
+        ws = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=p.device)
+        rows = torch.empty(B, STANDARD_COLS, dtype=torch.float64, device=p.device)
+        crop = (C.c_int32 * 4)(*self.crop) if self.crop is not None else None
+        _lib.check(L.rdm_eval_standard_f64(_lib.ptr(p), _lib.ptr(d), int(d.dtype == torch.float64), B, H, W, _lib.EVAL_ALIGN[self.align], self.min_depth,
+                                           self.max_depth, crop, _lib.ptr(rows), _lib.ptr(pred_out), _lib.ptr(ws), ws.numel() * 8, _lib.stream()))
+        return rows
+
+    def values_from_rows(self, rows):
+        """(N,16) rows (``compute_rows``, on the host or not) -> N entries: the list of this computer's metric values in float64, or None for a
+        sample without a valid pixel (n = 0), which the caller leaves out of its means."""
+        import math
+        r = torch.as_tensor(rows).detach().to("cpu", torch.float64).reshape(-1, STANDARD_COLS).tolist()
+        out = []
+        for row in r:
+            n = row[0]
+            if not n > 0:
+                out.append(None)
+                continue
+            g2, g1 = row[7] / n, row[8] / n
+            var = g2 - g1 * g1
+            v = {"delta1": row[1] / n, "delta2": row[2] / n, "delta3": row[3] / n, "abs_rel": row[4] / n, "sq_rel": row[5] / n,
+                 "rmse": math.sqrt(row[6] / n) if row[6] == row[6] else float("nan"), "rmse_log": math.sqrt(g2) if g2 == g2 else float("nan"),
+                 "silog": 100.0 * math.sqrt(max(var, 0.0)) if var == var else float("nan"), "log10": row[9] / n, "mae": row[10] / n, "scale": row[11]}
+            out.append([v[m] for m in self.names])
+        return out
+
+
 class MetricLogger:
     """log_train / log_val / log_test return the dicts the reference returns; `records` replaces self.log."""
 

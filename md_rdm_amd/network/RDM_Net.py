@@ -542,7 +542,9 @@ class DepthEstimationNet(BaseModel):
         self._ensure_flat(x.device)
         h, ws_bytes, oh, ow = self._plan(B, H, W)
         if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != x.device:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+            # zeroed once, when it is allocated: the plan never writes the padding columns of its buffers (logits: 180 of 192), and whoever reads a
+            # whole buffer (debug_buffer) must not see what an earlier owner of the block left there
+            self._ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=x.device)
         tensors = self._tensor_table()
         table = (C.c_void_p * len(tensors))(*[t.data_ptr() if t.numel() else None for t in tensors])
         logits = torch.empty(B, 180, oh, ow, dtype=torch.float32, device=x.device)
