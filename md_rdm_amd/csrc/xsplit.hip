@@ -19,8 +19,8 @@
 //  * image layout: subtile (8 pixels x 16 channels, 256 B) at 256 * (pixel_block * NCT + channel_tile); inside it pixel row p sits at
 //    32 * (p ^ 4 * (pixel_block & 1)).  The two 4x16 blocks a 32-lane half reads (k groups 8 pixels apart) then cover all 64 banks
 //    (conflict-free), and the staging stores (a 16-lane group writes a 4-pixel x 16-channel patch as 8-byte pieces) cover all 32.
-//  * staging = global -> registers (next slab in flight under the MFMAs) -> BatchNorm + ReLU -> split -> LDS; one image set, two
-//    barriers per slab, two workgroups per CU so one's staging runs beside the other's MFMAs.
+//  * staging = global -> registers (next slab in flight under the MFMAs) -> BatchNorm + ReLU -> split -> LDS; the 1x1 weight
+//    gradient keeps two image sets (one barrier per slab, one 8-wave workgroup per CU), the 3x3 one a single set and two workgroups per CU.
 #include <algorithm>
 #include <stdlib.h>
 
@@ -62,7 +62,17 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base0, const unsi
 
 // ---------------------------------------------------------------------------------------------
 // 1x1 weight gradient:  dW[n][c] += sum_m G[m][n] * f(X[m][c]),  f = ReLU(BatchNorm) or identity.
-// Workgroup = 4 waves, 128 (n) x 16*NT (c) outputs over a range of 32-pixel slabs; wave w owns rows 32w .. 32w+31 of the n tile.
+// Workgroup = 8 waves, 256 (n) x 16*NT (c) outputs over a range of 32-pixel slabs, ONE workgroup per CU.  Waves are tiled 4 (n) x 2 (c):
+// wave (wn, wc) owns rows 64 wn .. 64 wn + 63 and the column tiles [0, ceil(NT / 2)) (wc = 0) or [ceil(NT / 2), NT) (wc = 1) - 5 + 4 for
+// NT = 9 - i.e. 4 x 6 x 4 = 96 accumulator registers.  Per slab the CU stages 32 KB of G and <= 24 KB of X and its waves read 8 x 20 KB of
+// fragments.  TWO image sets: slab s + 1 is written to the other set while slab s is multiplied, one barrier per slab.  An output
+// accumulates its slabs in order and al bh, ah bl, ah bh within a slab, whatever the operand form: a split_k = 1 launch is deterministic.
+// (The kernel this replaced - 4 waves, 128 rows, one image set and two barriers per slab, two workgroups per CU, each wave reading the
+// whole X image: 2 x 40 KB staged and 2 x 112 KB of fragments per CU and slab - measured alone, us, old vs this: dense_e2 C = 96 / 192 / 336
+// 202 / 316 / 573 vs 195 / 273 / 484; dense_e3 C = 192 / 720 75 / 156 vs 73 / 146; dense_e4 C = 384 / 1248 / 2064 53 / 69 / 82 vs 50 / 61 / 77;
+// d_1 C = 1056 / 2160 55 / 56 vs 52 / 54: slower at no layer shape, so it is gone.  Those are float32 operands with the prologue; on the SPLIT ROWS
+// the training step hands over, the step's 78 launches take 5.93 vs 5.99 ms alone and 121.6 vs 121.6 us each in-step - unchanged - while their
+// HBM fetch falls 12 %; profiles/wgrad1x1_tiles_before.txt / _after.txt.  A staggered epilogue order was not tried.)
 // ---------------------------------------------------------------------------------------------
 struct XsWgradArgs {
   const float* G; int ldg; int N;
@@ -77,55 +87,55 @@ struct XsWgradArgs {
   int ct_c0[12], ct_nt[12];
 };
 
-constexpr int XS_BM = 128, XS_BK = 32, XS_NTMAX = 12;
-constexpr int XS_A_IMG = XS_BK * XS_BM * 2;                 // one plane of the gradient tile: 8 KB
+constexpr int XS_BM = 256, XS_BK = 32, XS_NTMAX = 12;
+constexpr int XS_A_IMG = XS_BK * XS_BM * 2;                 // one plane of the gradient tile: 16 KB
 constexpr int XS_B_IMG = XS_BK * XS_NTMAX * 16 * 2;         // one plane of the activation tile: <= 12 KB
+constexpr int XS_STAGE = 2 * XS_A_IMG + 2 * XS_B_IMG;       // one image set [A hi | A lo | B hi | B lo]: 56 KB
 
 template <int NT, int NP>
 __device__ __forceinline__ void xs_wgrad1x1_body(const XsWgradArgs& p, unsigned char* smem, int c0, int n0, int s_begin, int s_end) {
   constexpr int BN = NT * 16;
+  constexpr int TW = (NT + 1) / 2;                          // column tiles of a wave (the second half has NT / 2)
   constexpr int BPATCH = 8 * NT;                            // 4-pixel x 16-channel patches of the activation tile
-  constexpr int BL = (BPATCH + 15) / 16;                    // ... per 16-lane group
-  unsigned char* const Ahi = smem;
-  unsigned char* const Alo = smem + XS_A_IMG;
-  unsigned char* const Bhi = smem + 2 * XS_A_IMG;
-  unsigned char* const Blo = smem + 2 * XS_A_IMG + XS_B_IMG;
-  float* const Ssc = reinterpret_cast<float*>(smem + 2 * XS_A_IMG + 2 * XS_B_IMG);     // [BN] scale | [BN] shift
+  constexpr int BL = (BPATCH + 31) / 32;                    // ... per 16-lane group (32 groups)
+  float* const Ssc = reinterpret_cast<float*>(smem + 2 * XS_STAGE);                   // [BN] scale | [BN] shift
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wn = wave & 3, wc = wave >> 2;
+  const int t0 = wc ? TW : 0, ntw = wc ? NT / 2 : TW;
   const int l16 = lane & 15, g = lane >> 4;
   const int grp = tid >> 4, kq = l16 >> 2, jq = l16 & 3;
   const bool bnrelu = p.x_scale != nullptr;
   const __amdgpu_buffer_rsrc_t srdG = xsrd(p.G, p.g_bytes), srdX = xsrd(p.X, p.x_bytes);
 
   if (bnrelu) {
-    for (int i = tid; i < BN; i += 256) {
+    for (int i = tid; i < BN; i += 512) {
       const bool ok = c0 + i < p.C;
       Ssc[i] = ok ? p.x_scale[c0 + i] : 0.f;
       Ssc[BN + i] = ok ? p.x_shift[c0 + i] : 0.f;
     }
   }
 
-  // ---- staging maps.  A: patch (rg = (grp >> 3) + 2 it, ct = grp & 7): pixel row 4 rg + kq, channels 16 ct + 4 jq .. + 3 ----
+  // ---- staging maps.  A: patch (rg = (grp >> 4) + 2 it, ct = grp & 15): pixel row 4 rg + kq, channels 16 ct + 4 jq .. + 3 ----
   unsigned a_voff[4]; int a_row[4]; unsigned a_lds[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
-    const int rg = (grp >> 3) + 2 * it, ct = grp & 7;
+    const int rg = (grp >> 4) + 2 * it, ct = grp & 15;
     const int row = 4 * rg + kq, n = n0 + 16 * ct + 4 * jq;
     a_row[it] = n < p.N ? row : 0x40000000;
     a_voff[it] = (NP == 1 && p.g_bf16) ? (unsigned)row * (unsigned)(p.ldg * 2) + (unsigned)(n * 2) : (unsigned)row * (unsigned)(p.ldg * 4) + (unsigned)(n * 4);
     const int rb = row >> 3, pr = (row & 7) ^ ((rb & 1) << 2);
-    a_lds[it] = (unsigned)(256 * (rb * 8 + ct) + 32 * pr + 8 * jq);
+    a_lds[it] = (unsigned)(256 * (rb * 16 + ct) + 32 * pr + 8 * jq);
   }
   unsigned b_voff[BL]; int b_row[BL]; unsigned b_lds[BL]; int b_col[BL];
 #pragma unroll
   for (int it = 0; it < BL; ++it) {
-    const int pi = grp + 16 * it;
+    const int pi = grp + 32 * it;
     const int rg = pi / NT, ct = pi - rg * NT;
     const int row = 4 * rg + kq, cl = 16 * ct + 4 * jq;
     const bool ok = pi < BPATCH && c0 + cl < p.C;
     b_row[it] = ok ? row : 0x40000000;
-    b_col[it] = cl;
+    b_col[it] = pi < BPATCH ? cl : 0;
     b_voff[it] = (unsigned)row * (unsigned)(p.ldx * 4) + (unsigned)((c0 + cl) * 4);
     const int rb = row >> 3, pr = (row & 7) ^ ((rb & 1) << 2);
     b_lds[it] = pi < BPATCH ? (unsigned)(256 * (rb * NT + ct) + 32 * pr + 8 * jq) : 0u;
@@ -153,7 +163,11 @@ __device__ __forceinline__ void xs_wgrad1x1_body(const XsWgradArgs& p, unsigned 
       bhi[it] = ok ? __builtin_inff() : 0.f;
     }
   };
-  auto store_slab = [&]() {
+  auto store_slab = [&](unsigned char* st) {                  // st = the image set: [A hi | A lo | B hi | B lo]
+    unsigned char* const Ahi = st;
+    unsigned char* const Alo = st + XS_A_IMG;
+    unsigned char* const Bhi = st + 2 * XS_A_IMG;
+    unsigned char* const Blo = st + 2 * XS_A_IMG + XS_B_IMG;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       u32x2 hi, lo;
@@ -165,7 +179,7 @@ __device__ __forceinline__ void xs_wgrad1x1_body(const XsWgradArgs& p, unsigned 
     }
 #pragma unroll
     for (int it = 0; it < BL; ++it) {
-      if (BPATCH % 16 != 0 && it == BL - 1 && grp + 16 * it >= BPATCH) continue;
+      if (BPATCH % 32 != 0 && it == BL - 1 && grp + 32 * it >= BPATCH) continue;
       f32x4 v = rb[it];
       u32x2 hi, lo;
       if (NP == 3 && p.x_split) {                               // already activated and split by the producer (rows past M were loaded as zeros)
@@ -183,80 +197,86 @@ __device__ __forceinline__ void xs_wgrad1x1_body(const XsWgradArgs& p, unsigned 
     }
   };
 
-  // ---- fragment addresses: k group g reads pixel rows 8g .. 8g+7 as two 4-row blocks; lane (q, p) of a 16-lane group supplies row q,
-  // 8 bytes at channel 4p of the tile ----
+  // ---- fragment addresses (as in the 128-row body; the wave's first row tile and first column tile are folded in) ----
   const int fq = l16 >> 2, fp = l16 & 3;
-  const unsigned frA0 = (unsigned)(256 * (g * 8) + 32 * ((fq) ^ ((g & 1) << 2)) + 8 * fp);
-  const unsigned frA1 = (unsigned)(256 * (g * 8) + 32 * ((4 + fq) ^ ((g & 1) << 2)) + 8 * fp);
-  const unsigned frB0 = (unsigned)(256 * (g * NT) + 32 * ((fq) ^ ((g & 1) << 2)) + 8 * fp);
-  const unsigned frB1 = (unsigned)(256 * (g * NT) + 32 * ((4 + fq) ^ ((g & 1) << 2)) + 8 * fp);
+  const unsigned frA0 = (unsigned)(256 * (g * 16 + wn * 4) + 32 * ((fq) ^ ((g & 1) << 2)) + 8 * fp);
+  const unsigned frA1 = (unsigned)(256 * (g * 16 + wn * 4) + 32 * ((4 + fq) ^ ((g & 1) << 2)) + 8 * fp);
+  const unsigned frB0 = (unsigned)(256 * (g * NT + t0) + 32 * ((fq) ^ ((g & 1) << 2)) + 8 * fp);
+  const unsigned frB1 = (unsigned)(256 * (g * NT + t0) + 32 * ((4 + fq) ^ ((g & 1) << 2)) + 8 * fp);
 
-  f32x4 acc[2][NT];
+  f32x4 acc[4][TW];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int t = 0; t < NT; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < TW; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   load_slab(s_begin);
   __syncthreads();                                            // the BatchNorm table is in place
-  store_slab();
+  store_slab(smem);
+  if (s_begin + 1 < s_end) load_slab(s_begin + 1);
   __syncthreads();
   for (int s = s_begin; s < s_end; ++s) {
-    const bool more = s + 1 < s_end;
-    if (more) load_slab(s + 1);                               // in flight under this slab's MFMAs
-    bf16x8 ah[2], al[2];
+    const int cur = (s - s_begin) & 1;
+    const unsigned char* const Ahi = smem + cur * XS_STAGE;
+    const unsigned char* const Alo = Ahi + XS_A_IMG;
+    const unsigned char* const Bhi = Ahi + 2 * XS_A_IMG;
+    const unsigned char* const Blo = Ahi + 2 * XS_A_IMG + XS_B_IMG;
+    bf16x8 ah[4], al[4];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int imm = 256 * (wave * 2 + i);
-      ah[i] = tr_frag(Ahi + frA0, Ahi + frA1, imm);
-      al[i] = tr_frag(Alo + frA0, Alo + frA1, imm);
+    for (int i = 0; i < 4; ++i) {
+      ah[i] = tr_frag(Ahi + frA0, Ahi + frA1, 256 * i);
+      if (NP == 3) al[i] = tr_frag(Alo + frA0, Alo + frA1, 256 * i);
     }
     bf16x8 bh[2], bl[2];
     bh[0] = tr_frag(Bhi + frB0, Bhi + frB1, 0);
-    bl[0] = tr_frag(Blo + frB0, Blo + frB1, 0);
+    if (NP == 3) bl[0] = tr_frag(Blo + frB0, Blo + frB1, 0);
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int cur = t & 1;
-      if (t + 1 < NT) {
-        bh[cur ^ 1] = tr_frag(Bhi + frB0, Bhi + frB1, 256 * (t + 1));
-        bl[cur ^ 1] = tr_frag(Blo + frB0, Blo + frB1, 256 * (t + 1));
+    for (int t = 0; t < TW; ++t) {
+      if (NT % 2 != 0 && t == TW - 1 && t >= ntw) continue;   // the shorter half of an odd NT (wave-uniform)
+      const int cb = t & 1;
+      if (t + 1 < TW && (NT % 2 == 0 || t + 1 < TW - 1 || t + 1 < ntw)) {
+        bh[cb ^ 1] = tr_frag(Bhi + frB0, Bhi + frB1, 256 * (t + 1));
+        if (NP == 3) bl[cb ^ 1] = tr_frag(Blo + frB0, Blo + frB1, 256 * (t + 1));
       }
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
+      for (int i = 0; i < 4; ++i) {
         if (NP == 3) {
-          acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh[cur], acc[i][t], 0, 0, 0);
-          acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[cur], acc[i][t], 0, 0, 0);
+          acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh[cb], acc[i][t], 0, 0, 0);
+          acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[cb], acc[i][t], 0, 0, 0);
         }
-        acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[cur], acc[i][t], 0, 0, 0);
+        acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[cb], acc[i][t], 0, 0, 0);
       }
     }
-    __syncthreads();                                          // every wave is past its reads of the images
-    if (more) {
-      store_slab();
-      __syncthreads();
+    // slab s + 1 (in registers since the last iteration) goes to the other set: every wave left that set at the barrier that ended
+    // iteration s - 1; slab s + 2 then flies under the barrier and the next slab's MFMAs
+    if (s + 1 < s_end) {
+      store_slab(smem + (cur ^ 1) * XS_STAGE);
+      if (s + 2 < s_end) load_slab(s + 2);
     }
+    __syncthreads();
   }
 
   // ---- split-K epilogue: f32 atomics into the (pre-zeroed) gradient; D row = 4 g + r (n), column = l16 (c) ----
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int c = c0 + 16 * t + l16;
+  for (int t = 0; t < TW; ++t) {
+    if (NT % 2 != 0 && t == TW - 1 && t >= ntw) continue;
+    const int c = c0 + 16 * (t0 + t) + l16;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wave * 32 + i * 16 + g * 4 + r;
+        const int n = n0 + wn * 64 + i * 16 + g * 4 + r;
         if (c < p.C && n < p.N) atomicAdd(p.dW + (long)n * p.ldw + c, acc[i][t][r]);
       }
   }
 }
 
-// (a narrow instantiation - column tiles of <= 96 channels, 162 registers, three workgroups per CU - was measured against this one: 0.17 vs 0.19 ms
+// (a narrow instantiation - column tiles of <= 96 channels, 162 registers, three workgroups per CU - was measured against the 128-row kernel: 0.17 vs 0.19 ms
 // at dense_e2 C = 96 and 0.055 vs 0.071 at dense_e3 C = 192, but 0.29 vs 0.24 at C = 144 and 0.57 vs 0.52 at C = 336: occupancy is not what
-// holds the kernel; per 32-pixel slab its four waves read 112 KB of fragments from LDS for 1 152 MFMA cycles each - the LDS is as busy as the pipe)
+// held that kernel; per 32-pixel slab its four waves read 112 KB of fragments from LDS for 1 152 MFMA cycles each - the LDS was as busy as the pipe)
 template <int NP>
-__global__ __launch_bounds__(256, 2) void xs_wgrad1x1_kernel(XsWgradArgs p) {
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * XS_A_IMG + 2 * XS_B_IMG + 2 * XS_NTMAX * 16 * 4];
+__global__ __launch_bounds__(512, 1) void xs_wgrad1x1_kernel(XsWgradArgs p) {
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * XS_STAGE + 2 * XS_NTMAX * 16 * 4];
   // work item = (column tile, row tile, K split), column tile fastest; XCD x works through a contiguous range of items so that the
   // column tiles sharing one gradient tile meet in one L2 (placement affects speed only)
   const unsigned total = gridDim.x, L = blockIdx.x, x = L & 7u, q = total >> 3, r = total & 7u;
@@ -1225,18 +1245,20 @@ int launch_xs_wgrad1x1(const WgradArgs& a, hipStream_t s) {
   }
   k.n_ctiles = nct;
   const long tiles = (long)nct * cdiv(a.N, XS_BM), kslabs = (M + XS_BK - 1) / XS_BK;
-  // K split: ONE round of the 512 resident workgroups (2 per CU), at least 16 slabs of 32 pixels per split (the f32 atomics of a split's epilogue
-  // cost as much as ~8 slabs at dense_e4's widths).  Swept per shape (alone, us; auto = the generic pick_split_k this replaced): dense_e3 C = 480:
-  // 102 at 15 splits vs 148 auto; C = 720: 147 at 11 vs 170; dense_e4 C = 432 / 768 / 1248 / 1632: 41 / 55 / 66 / 73 at 8 vs 71 / 80 / 82 / 85;
-  // dense_e2 C = 96 / 192: 185 / 291 at 23 vs 206 / 302; a second round (24 splits of 22 tiles) costs 40 % at once
-  if (a.split_k > 0) k.split_k = a.split_k;
-  else if (tiles > 512) k.split_k = pick_split_k(tiles, kslabs / 2, 256 * 2);
-  else k.split_k = (int)std::max<long>(1, std::min<long>(512 / tiles, kslabs / 16));
-  if (k.split_k > kslabs) k.split_k = (int)kslabs;
+  // K split: ONE round of the 256 resident workgroups (1 per CU), at least 16 slabs of 32 pixels per split (the f32 atomics of a split's epilogue cost as
+  // much as ~8 slabs at dense_e4's widths; the 128-row kernel swept, alone, us, one round vs the generic pick_split_k: dense_e3 C = 480: 102 vs 148;
+  // dense_e4 C = 432 / 1632: 41 / 73 vs 71 / 85; a second round costs 40 % at once).  Whether a shape splits at all is still decided on the 128-row
+  // tiling the kernel had (tiles128, 512 slots): the split1 / splitK class of every shape - its census key - stays what it was.
+  const long tiles128 = (long)nct * cdiv(a.N, 128);
+  const long split128 = tiles128 > 512 ? pick_split_k(tiles128, kslabs / 2, 256 * 2) : std::max<long>(1, std::min<long>(512 / tiles128, kslabs / 16));
+  long split = 1;
+  if (split128 > 1) split = std::max<long>(2, tiles > 256 ? pick_split_k(tiles, kslabs / 2, 256) : std::min<long>(256 / tiles, kslabs / 16));
+  if (a.split_k > 0) split = a.split_k;
+  k.split_k = (int)std::min<long>(split, kslabs);
   void* prof = profile_begin(s, 2.0 * (double)M * a.N * a.C, 13);
   RDM_CENSUS("xs_wgrad1x1_kernel/x%d/%s/%s%s", a.xsplit == 1 ? 1 : 3, a.x_scale ? "bn1" : "bn0", k.split_k > 1 ? "splitK" : "split1", a.g_split && a.x_split ? "/rowsGX" : a.g_split ? "/rowsG" : a.x_split ? "/rowsX" : "");
-  if (a.xsplit == 1) hipLaunchKernelGGL(xs_wgrad1x1_kernel<1>, dim3((unsigned)(tiles * k.split_k)), dim3(256), 0, s, k);
-  else hipLaunchKernelGGL(xs_wgrad1x1_kernel<3>, dim3((unsigned)(tiles * k.split_k)), dim3(256), 0, s, k);
+  if (a.xsplit == 1) hipLaunchKernelGGL(xs_wgrad1x1_kernel<1>, dim3((unsigned)(tiles * k.split_k)), dim3(512), 0, s, k);
+  else hipLaunchKernelGGL(xs_wgrad1x1_kernel<3>, dim3((unsigned)(tiles * k.split_k)), dim3(512), 0, s, k);
   profile_end(prof, s);
   RDM_LAUNCH_OK();
   return 0;

@@ -167,3 +167,7 @@ if which in ("wg1", "all"):
         wg1(16, 57, 76, 2736, cin, 384)
     for cin in (192, 336, 480, 720):
         wg1(16, 29, 38, 1392, cin, 768)
+    for cin in (384, 1248, 2064):                         # dense_e4
+        wg1(16, 15, 19, 720, cin, 2112)
+    for cin in (1056, 2160):                              # d_1
+        wg1(16, 8, 10, 384, cin, 2208)
