@@ -316,8 +316,20 @@ __global__ __launch_bounds__(512, 1) void xs_wgrad1x1_kernel(XsWgradArgs p) {
 //    channels of one pixel - the gate's Y read and the dZ store are 16-byte accesses, two of them side by side cover a pixel's 128-byte
 //    line - and every wave owns its 32 channels for ALL 192 pixels: the BatchNorm-backward sums need no cross-wave reduction.
 //  * a work item = (pixel tile, group of column tiles): the image staging and the address set-up are paid once per group.
+//  * the epilogue runs in 6 chunks of (2 pixel tiles x the wave's 2 channel tiles) with the gate values of TWO chunks in flight ahead of
+//    their use, the first issued at the head of the last k-step (they do not depend on the accumulators).  Before, the epilogue was 4
+//    batches of 6 loads, each waited for in full before its mask, sums and stores: k loop and epilogue added (0.32 + 0.39 ms of a 0.64 ms
+//    dense_e2 launch).  Alone on the chip, parent -> this: dense_e2 0.636 -> 0.587 ms, dense_e3 0.092 -> 0.075, dense_e4 0.032 -> 0.028,
+//    d_1 0.029 -> 0.026 (profiles/dgrad3x3_overlap_before.txt / _after.txt).  The registers came from what hipcc carried from item to
+//    item for nothing: the 14 unpacked tap shifts and sums formed from them, the staging maps, the per-tile gate offsets, store addresses
+//    and statistics addresses (all now derived inside the item from opaque copies of the lane index: 256 -> 241 VGPRs, no scratch).
+//    Tried and lost on the way (compile-time findings, never run): the first TWO chunks under the last two k-steps - 29 .. 75 registers
+//    spilled, with a reload and s_waitcnt vmcnt(0) in front of ds_reads of the k loop; the image base made opaque once per k-step - hipcc
+//    then holds more fragment addresses, not fewer (70 .. 96 spilled).  NOT built: the 2 x 2 wave re-tiling (64 channels x 96 pixels per
+//    wave, the weight slab through LDS) and a second, half-size accumulator set.
 // =============================================================================================
-constexpr int XD_BM = 192, XD_MT = XD_BM / 16, XD_KSTEPS = 14, XD_SLOT = 96, XD_BN = 128, XD_EB = 6;
+constexpr int XD_BM = 192, XD_MT = XD_BM / 16, XD_KSTEPS = 14, XD_SLOT = 96, XD_BN = 128;
+constexpr int XD_EC = 2, XD_NCH = XD_MT / XD_EC, XD_EA = 2, XD_EK = 1;      // epilogue: pixel tiles per chunk, chunks, chunks of gate values in flight ahead of their use
 
 struct XsDgrad3Args {
   const float* G; int ldg;
@@ -357,7 +369,6 @@ template <bool MASK, int NP>
 __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char xs_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l16 = lane & 15, g = lane >> 4;
   const int W = p.W, HW = p.H * p.W;
   // work items = (pixel tile, 128-channel column tile), column tile fastest; workgroup b takes the contiguous range [b T / G, (b + 1) T / G)
   // of them (G = gridDim.x = every workgroup slot of the chip: all resident at once, balanced to +-1 item) and re-stages the gradient
@@ -370,16 +381,14 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
 
   // k-step j -> the lane's chunk: offset of (tap shift, 8-channel group), biased by +32768, two per register
   unsigned dpk[XD_KSTEPS / 2];
-  const int hi2 = g >> 1;
 #pragma unroll
   for (int j = 0; j < XD_KSTEPS; ++j) {
-    const int ch = 4 * j + g, tap = ch < 54 ? ch / 6 : 0, r = tap / 3, q = tap - 3 * r;
+    const int ch = 4 * j + (lane >> 4), tap = ch < 54 ? ch / 6 : 0, r = tap / 3, q = tap - 3 * r;
     const unsigned d = (unsigned)(((1 - r) * W + (1 - q)) * XD_SLOT + (ch - 6 * (ch / 6)) * 16 + 32768);
     if (j & 1) dpk[j >> 1] |= d << 16; else dpk[j >> 1] = d;
   }
   int base0 = 0; int vm[XD_MT / 3];                          // pixel tile i: image offset base0 + 16 * 96 * i; 9 validity bits at bit 10 * (i % 3) of vm[i / 3]
   int cur_mt = -1, m0 = 0;
-  const unsigned wv = (unsigned)(lane * 16);
   for (int it = it0; it < it1; ++it) {
     const int mt = it / p.ctiles, tile = it - mt * p.ctiles;
     if (mt != cur_mt) {
@@ -388,18 +397,20 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
       __syncthreads();                                          // every wave is past its reads of the previous images
       // ---- gradient tile -> the two bf16 images ----
       const int total4 = (p.nslots - 1) * 12, pbase = m0 - (W + 1);
+      int ts = tid;
+      asm volatile("" : "+v"(ts));                              // (the staging maps are recomputed per pixel tile, not held in registers through the k loops)
       for (int b0 = 0; b0 < total4; b0 += 256 * 6) {
         f32x4 v[6];
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-          const int idx = b0 + u * 256 + tid, slot = idx / 12, quad = idx - slot * 12;
+          const int idx = b0 + u * 256 + ts, slot = idx / 12, quad = idx - slot * 12;
           const int pix = pbase + slot;
           const bool ok = idx < total4 && pix >= 0 && pix < p.M;
           v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdG, (int)(ok ? (unsigned)pix * (unsigned)(p.ldg * 4) + (unsigned)(quad * 16) : XOOB), 0, 0));
         }
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-          const int idx = b0 + u * 256 + tid, slot = idx / 12, quad = idx - slot * 12;
+          const int idx = b0 + u * 256 + ts, slot = idx / 12, quad = idx - slot * 12;
           if (idx < total4) {
             u32x2 hi, lo;
             split4(v[u][0], v[u][1], v[u][2], v[u][3], hi, lo);
@@ -408,12 +419,12 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
           }
         }
       }
-      if (tid < 24) *reinterpret_cast<u32x2*>(xs_smem + (tid % 12) * 8 + (tid / 12) * p.plane_bytes) = u32x2{0u, 0u};      // slot 0 of both planes
+      if (ts < 24) *reinterpret_cast<u32x2*>(xs_smem + (ts % 12) * 8 + (ts / 12) * p.plane_bytes) = u32x2{0u, 0u};      // slot 0 of both planes
       // ---- per lane: pixel tile i -> image offset of the pixel's slot (biased by -32768) and the validity of its 9 taps ----
-      base0 = (l16 + W + 1 + 1) * XD_SLOT - 32768;
+      base0 = ((ts & 15) + W + 1 + 1) * XD_SLOT - 32768;
 #pragma unroll
       for (int i = 0; i < XD_MT; ++i) {
-        const int m = m0 + i * 16 + l16;
+        const int m = m0 + i * 16 + (ts & 15);
         const bool ok = m < p.M;
         const int b = m / HW, rem = m - b * HW, y = rem / W, x = rem - y * W;
         int v = 0;
@@ -429,7 +440,13 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
     }
     const int ct16 = tile * (XD_BN / 16) + 2 * wave;            // this wave's two 16-channel tiles
     if (ct16 * 16 >= p.Cb) continue;                            // (wave-uniform) ragged last column tile
+    int ln = lane;                                              // (the item's lane-derived values start from an opaque copy: nothing of them is carried from item to item)
+    asm volatile("" : "+v"(ln));
+    const int l16 = ln & 15, g = ln >> 4, hi2 = g >> 1;
+    const unsigned wv = (unsigned)(ln * 16);
     asm volatile("" : "+v"(base0));                             // (keeps the 168 fragment addresses from being hoisted out of the item loop into registers)
+#pragma unroll
+    for (int q = 0; q < XD_KSTEPS / 2; ++q) asm volatile("" : "+v"(dpk[q]));      // (and the 14 unpacked shifts, with the per-tile sums hipcc forms from them)
     f32x4 acc[XD_MT][2];
 #pragma unroll
     for (int i = 0; i < XD_MT; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -444,6 +461,28 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
     };
     // (the hardware range check looks at the VECTOR offset: the tile index travels there, so a tile past Cb reads as zeros)
     const bool t1ok = (ct16 + 1) * 16 < p.Cb;
+    // ---- the gate values of the epilogue: they do not depend on the accumulators, so they are fetched AHEAD of their use.  The wave's 192
+    // pixels are walked in XD_NCH chunks of XD_EC pixel tiles x both channel tiles (the two 16-byte loads of a pixel lie side by side: one
+    // 128-byte line); a ring of XD_EA + 1 chunk buffers keeps XD_EA chunks in flight: chunks 0 and 1 are issued at the head of the last two
+    // k-steps (their registers are the weight buffer that has just died and what the address hoisting used to take), chunk c + XD_EA before
+    // chunk c's mask, sums and stores.  (Loads in buffer form: ONE 32-bit offset register per channel tile, the pixel tile's row offset
+    // travels in the scalar offset; a pixel or channel tile past the end becomes an out-of-range vector offset and reads as zeros.)
+    f32x4 xv[XD_EA + 1][XD_EC][2];
+    f32x4 xs[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, xt[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    const int c40 = ct16 * 16 + 4 * g;                            // the lane's 4 channels of tile t: c40 + 16 t
+    int ml = m0 + l16;                                          // the lane's pixel of pixel tile 0
+    const unsigned vx0 = (unsigned)ml * (unsigned)(p.ldx * 4) + (unsigned)(c40 * 4);
+    const int osz = (NP == 1 && p.out_bf16) ? 2 : 4;            // dZ: ONE 32-bit lane offset, the pixel tile's row offset and the channel tile travel in the uniform base
+    const unsigned vo0 = (unsigned)ml * (unsigned)(p.ldc * osz) + (unsigned)(c40 * osz);
+    auto gate_load = [&](int c) {
+#pragma unroll
+      for (int u = 0; u < XD_EC; ++u)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int i = c * XD_EC + u;
+          xv[c % (XD_EA + 1)][u][t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)(((t == 0 || t1ok) && ml + i * 16 < p.M) ? vx0 + 64u * t : XOOB), i * 16 * p.ldx * 4, 0));
+        }
+    };
     load_w(0, wf[0]);
     // gradient fragments of (k-step j, pixel tile i): software pipeline - the pair of ds_read_b128 of tile i + 1 is issued BEFORE the six
     // MFMAs of tile i (pinned: left alone, hipcc sinks every read next to its first use and the matrix pipe waits for LDS 12 times a step)
@@ -459,6 +498,7 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
 #pragma unroll
     for (int j = 0; j < XD_KSTEPS; ++j) {
       if (j + 1 < XD_KSTEPS) load_w(j + 1, wf[(j + 1) & 1]);
+      if (MASK && j >= XD_KSTEPS - XD_EK) gate_load(j - (XD_KSTEPS - XD_EK));
 #pragma unroll
       for (int i = 0; i < XD_MT; ++i) {
         const int cur = (j * XD_MT + i) & 1;
@@ -477,58 +517,59 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
       }
     }
 
-    // ---- epilogue: D row = 4 g + r (channel), column = l16 (pixel): a lane owns channels c4 .. c4 + 3 of pixel m ----
+    // ---- epilogue: D row = 4 g + r (channel), column = l16 (pixel): a lane owns channels c4 .. c4 + 3 of pixel m.  Per channel tile the
+    // pixel tiles are summed in ascending order, whatever the chunking ----
+    f32x4 s0[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, s1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    if (MASK) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int c4 = (ct16 + t) * 16 + 4 * g;
-      const bool cok = t == 0 || t1ok;
-      f32x4 xs = {0.f, 0.f, 0.f, 0.f}, xt = {0.f, 0.f, 0.f, 0.f};
-      if (MASK && cok) { xs = *reinterpret_cast<const f32x4*>(p.x_scale + c4); xt = *reinterpret_cast<const f32x4*>(p.x_shift + c4); }
-      f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-      // (gate loads in buffer form: ONE 32-bit offset register, the pixel tile's row offset travels in the scalar offset; a pixel or channel
-      // tile past the end becomes an out-of-range vector offset and reads as zeros)
-      const unsigned vx = (unsigned)(m0 + l16) * (unsigned)(p.ldx * 4) + (unsigned)(c4 * 4);
+      for (int t = 0; t < 2; ++t)
+        if (t == 0 || t1ok) { xs[t] = *reinterpret_cast<const f32x4*>(p.x_scale + c40 + 16 * t); xt[t] = *reinterpret_cast<const f32x4*>(p.x_shift + c40 + 16 * t); }
 #pragma unroll
-      for (int i0 = 0; i0 < XD_MT; i0 += XD_EB) {
-        f32x4 xv[XD_EB];
-        if (MASK) {
+      for (int c = XD_EK; c < XD_EA; ++c) gate_load(c);
+    }
 #pragma unroll
-          for (int u = 0; u < XD_EB; ++u)
-            xv[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)((cok && m0 + (i0 + u) * 16 + l16 < p.M) ? vx : XOOB), (i0 + u) * 16 * p.ldx * 4, 0));
-        }
+    for (int c = 0; c < XD_NCH; ++c) {
+      if (MASK && c + XD_EA < XD_NCH) { gate_load(c + XD_EA); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
-        for (int u = 0; u < XD_EB; ++u) {
-          const int i = i0 + u;
-          const bool ok = cok && m0 + i * 16 + l16 < p.M;
+      for (int u = 0; u < XD_EC; ++u)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int i = c * XD_EC + u;
+          const bool ok = (t == 0 || t1ok) && ml + i * 16 < p.M;
+          unsigned char* const orow = reinterpret_cast<unsigned char*>(p.out) + ((long)i * 16 * p.ldc + 16 * t) * osz;
           f32x4 v = acc[i][t];
           if (MASK) {
-            const f32x4 x = xv[u];                                 // zeros where !ok: nothing of a dead element reaches the sums
+            const f32x4 x = xv[c % (XD_EA + 1)][u][t];              // zeros where !ok: nothing of a dead element reaches the sums
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaf(x[e], xs[e], xt[e]) > 0.f ? v[e] : 0.f;
-            if (ok) { s0 += v; s1 += v * x; }
+            for (int e = 0; e < 4; ++e) v[e] = fmaf(x[e], xs[t][e], xt[t][e]) > 0.f ? v[e] : 0.f;
+            if (ok) { s0[t] += v; s1[t] += v * x; }
           }
           // (plain global stores ON PURPOSE: with buffer-form stores here, the shuffles and the exec-masked atomics of the statistics below
           // left wrong values in lanes 12-15 of some stored registers on MI355X / ROCm 7.2 - measured, cause not established; the same
           // epilogue with global_store_dwordx4 is exact)
           if (NP == 1 && p.out_bf16) {
             const bf16x2 lo2 = {(__bf16)v[0], (__bf16)v[1]}, hi2 = {(__bf16)v[2], (__bf16)v[3]};
-            if (ok) *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(p.out) + (long)(m0 + i * 16 + l16) * p.ldc + c4) = u32x2{__builtin_bit_cast(unsigned, lo2), __builtin_bit_cast(unsigned, hi2)};
-          } else if (ok) *reinterpret_cast<f32x4*>(p.out + (long)(m0 + i * 16 + l16) * p.ldc + c4) = v;
+            if (ok) *reinterpret_cast<u32x2*>(orow + vo0) = u32x2{__builtin_bit_cast(unsigned, lo2), __builtin_bit_cast(unsigned, hi2)};
+          } else if (ok) *reinterpret_cast<f32x4*>(orow + vo0) = v;
         }
-      }
-      if (MASK) {
+    }
+    if (MASK) {
+      const int sl = 4 * g + l16;                               // lane l16 < 4 of each 16 reports channel 4 g + l16 of the tile
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int c4 = ct16 * 16 + 16 * t + sl;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float a = s0[e], b = s1[e];
+          float a = s0[t][e], b = s1[t][e];
           a += __shfl_xor(a, 1); b += __shfl_xor(b, 1);
           a += __shfl_xor(a, 2); b += __shfl_xor(b, 2);
           a += __shfl_xor(a, 4); b += __shfl_xor(b, 4);
           a += __shfl_xor(a, 8); b += __shfl_xor(b, 8);
-          if (l16 == e) { s0[0] = a; s1[0] = b; }               // lane e of each 16 keeps channel c4 + e
+          if (l16 == e) { s0[t][0] = a; s1[t][0] = b; }         // lane e of each 16 keeps channel c4 + e
         }
-        if (l16 < 4 && cok) {
-          atomicAdd(p.stat0 + c4 + l16, (double)s0[0]);
-          atomicAdd(p.stat1 + c4 + l16, (double)s1[0]);
+        if (l16 < 4 && (t == 0 || t1ok)) {
+          atomicAdd(p.stat0 + c4, (double)s0[t][0]);
+          atomicAdd(p.stat1 + c4, (double)s1[t][0]);
         }
       }
     }

@@ -162,6 +162,8 @@ if which in ("dg1", "all"):
 if which in ("dg3", "all"):
     dg3(16, 57, 76, 2736)
     dg3(16, 29, 38, 1392)
+    dg3(16, 15, 19, 720)                                  # dense_e4
+    dg3(16, 8, 10, 384)                                   # d_1
 if which in ("wg1", "all"):
     for cin in (96, 144, 192, 240, 288, 336):
         wg1(16, 57, 76, 2736, cin, 384)
