@@ -235,6 +235,11 @@ def make_pred(w, A, cuda, relative_only):
         for i, v in enumerate(yp.views()):
             A[i] = v
         return A
+    if pyr is not None and pyr.kind == "log_pending":
+        # not the fused launch (a relative row, or several weights at a level): the views still hold the RAW levels, and the general branch
+        # expects what the reference's make_matrix hands it - their logs
+        for i in range(len(A)):
+            A[i] = torch.log(A[i])
     for i in range(len(A)):
         B, M = A[i].shape[0], A[i].shape[2]
         s = int(math.sqrt(M))
