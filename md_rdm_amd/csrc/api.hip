@@ -331,8 +331,7 @@ int rdm_conv2d_wgrad_x3(const rdm_conv_desc* d, const float* dy, const float* x,
 size_t rdm_conv3x3_wino_workspace_bytes(int32_t channels, int32_t batch, int32_t h, int32_t w, int32_t split_k) {
   if (channels <= 0 || channels % 16 || batch <= 0 || h <= 0 || w <= 0 || split_k < 0) return 0;
   const int T = batch * ((h + 1) / 2) * ((w + 1) / 2);
-  const int split = split_k > 0 ? split_k : wino_pick_split(T, channels / 16);
-  return wino_fwd_workspace_bytes(channels, (long)batch * h * w, split);
+  return wino_fwd_workspace_bytes(channels, (long)batch * h * w, wino_fwd_planes(T, channels / 16, split_k));
 }
 
 int rdm_conv3x3_wino_fwd(const rdm_conv_desc* d, const float* x, const float* w, const float* bn_scale, const float* bn_shift, float* y,

@@ -224,7 +224,7 @@ struct NetImpl {
   // Winograd F(2x2, 3x3) for the 3x3 convs of the blocks with many pixels (wino.hip): transformed weights per layer (formed on the side
   // stream at the start of forward) and one scratch for the per-split partial outputs
   bool wino_fwd[4] = {false, false, false, false}, wino_wg[4] = {false, false, false, false};
-  int wino_split[4] = {1, 1, 1, 1}, wino_split_x6[4] = {1, 1, 1, 1};
+  int wino_split_x6[4] = {1, 1, 1, 1};
   int opt_wino_x6 = 0;         // RDM_NET_OPT_WINO_X6: the Winograd forward of those blocks on the bf16x6 kernel (float32-equivalent, bf16 matrix pipe)
   size_t winoPartial = 0, winoPartialFloats = 0;
   size_t winoVy = 0, winoVyFloats = 0, winoQ = 0, winoQFloats = 0;     // weight-gradient scratch (side stream: one launch at a time)
@@ -369,9 +369,8 @@ struct NetImpl {
       wino_wg[b] = bg[b].M >= 12288 && bg[b].cb % 16 == 0;
       if (!wino_fwd[b]) continue;
       const int T = B * ((bg[b].H + 1) / 2) * ((bg[b].W + 1) / 2);
-      wino_split[b] = wino_pick_split(T, bg[b].cb / 16);
       wino_split_x6[b] = wino_pick_split(T, bg[b].cb / 16, true);
-      const int sp = std::max(wino_split[b], wino_split_x6[b]);              // options arrive after the layout: sized for either kernel
+      const int sp = std::max(wino_fwd_planes(T, bg[b].cb / 16, 0), wino_split_x6[b]);      // options arrive after the layout: sized for either kernel (f32: its piece planes)
       if (sp > 1) winoPartialFloats = std::max(winoPartialFloats, (size_t)sp * bg[b].M * 48);
       winoU[b].resize(kBlocks[b].layers);
       for (auto& o : winoU[b]) o = a.take<unsigned char>(std::max(wino_u_bytes(bg[b].cb, false), wino_u_bytes(bg[b].cb, true)));
@@ -663,7 +662,7 @@ int forward_block(NetImpl& n, int b, void* ws, void* const* T, int training, hip
       wv.A = Y; wv.lda = g.cb; wv.C = g.cb; wv.a_scale = bn2; wv.a_shift = bn2 + g.cb; wv.U = at<float>(ws, n.winoU[b][i]);
       wv.out = blk + cin; wv.ldc = g.ctot; wv.N = GROWTH; wv.B = n.B; wv.H = g.H; wv.W = g.W;
       wv.x6 = R.wino_x6;
-      wv.split = wv.x6 ? n.wino_split_x6[b] : n.wino_split[b]; wv.partial = at<float>(ws, n.winoPartial); wv.partial_floats = n.winoPartialFloats;
+      wv.split = wv.x6 ? n.wino_split_x6[b] : 0; wv.partial = at<float>(ws, n.winoPartial); wv.partial_floats = n.winoPartialFloats;
       if (training) { wv.stat0 = bst + cin; wv.stat1 = bst + g.ctot + cin; }
       if ((rc = launch_conv3x3_wino_fwd(wv, s))) return rc;
     } else {

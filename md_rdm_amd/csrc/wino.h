@@ -9,8 +9,8 @@ struct WinoConv {
   const float* U;                                 // launch_wino_weight output, 16 * 48 * C floats
   float* out; int ldc; int N;                     // output slice (pixel stride ldc), N <= 48 channels
   int B, H, W;
-  int split;                                      // 0: launcher's choice; > 1 needs `partial`
-  float* partial; size_t partial_floats;          // scratch for the per-split partial outputs, split * B*H*W * 48 floats
+  int split;                                      // 0: launcher's choice.  x6: K splits (> 1 needs `partial`); f32: the workgroup count G of the persistent walk
+  float* partial; size_t partial_floats;          // scratch for the partial outputs: x6 split * B*H*W * 48 floats, f32 wino_fwd_planes(..) * B*H*W * 48
   double* stat0; double* stat1;                   // optional: += sum / sum of squares of the output per channel
   int x6;                                         // 1: the bf16x6 kernel (float32-equivalent, bf16 matrix pipe); U then in launch_wino_weight(..., x6 = true) form
 };
@@ -28,7 +28,8 @@ size_t wino_wgrad_part_floats(int B, int H, int W, int C);
 int launch_conv3x3_wino_wgrad(const WinoWgrad& a, hipStream_t s);
 size_t wino_u_bytes(int C, bool x6);                                       // transformed-weight image of one layer
 size_t wino_fwd_workspace_bytes(int C, long M, int split, bool x6 = false);
-int wino_pick_split(int tiles, int nslab, bool x6 = false);
+int wino_pick_split(int tiles, int nslab, bool x6 = false);               // K split of the bf16x6 kernel
+int wino_fwd_planes(int tiles, int nslab, int groups);                     // f32 kernel: planes of `partial` a launch with WinoConv::split = groups needs (1: none)
 int launch_wino_weight(const float* w_packed, long wtap, int ldw, int N, int C, float* U, hipStream_t s, bool x6 = false);
 int launch_conv3x3_wino_fwd(const WinoConv& a, hipStream_t s);
 }  // namespace rdm

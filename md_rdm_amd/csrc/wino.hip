@@ -25,6 +25,13 @@
 //    kernel's 31 - and the kernel runs at the L2 -> CU feed rate, 1.65 ms against the direct kernel's 1.66 ms (round 3; removed again).
 //  * split-K writes per-split partial OUTPUTS (the output transform is linear) with plain stores; a small ordered reduction adds them
 //    in a fixed order and takes the per-channel statistics of the sum - deterministic, and 5x the byte rate of f32 atomics.
+//  * the f32 forward WALKS its work persistently: the (tile block, 16-channel slab) units, tile block major, are dealt to 256 workgroups (one per
+//    CU) as contiguous ranges by arithmetic on blockIdx.x alone - no tickets, no atomics, nobody waits for anybody.  Inside a range a workgroup
+//    keeps its accumulators over consecutive slabs of a tile block, transforms and stores once per piece, and gathers the next block's first slab
+//    under that output transform.  A tile block cut by range ends goes to the partial buffer as piece planes (<= ceil(nslab / floor(U / G)) + 1: 2
+//    at dense_e2, where the K split wrote 10); k_wino_reduce_pieces sums a block's pieces in slab order.  Measured (profiles/wino_persistent_*.txt):
+//    dense_e2 0.885 -> 0.793 ms per call, dense_e3 0.138 -> 0.132, the B=16 228x304 train step 47.54 -> 47.00 ms; 253 registers, no scratch.
+//    Deterministic mode walks the fixed K chunks of wino_pick_split instead (one piece per chunk): the bits of its sums are the recorded ones.
 #include <algorithm>
 #include <stdlib.h>
 
@@ -99,11 +106,22 @@ struct WinoFwdArgs {
   const float* A; int lda; int C;                 // raw NHWC input, contracted channels (multiple of 16)
   const float* a_scale; const float* a_shift;     // consumer BatchNorm + ReLU (may be NULL)
   const float* U;                                 // transformed weights, fragment order
-  float* out; int ldc; int N;                     // split == 1: the output slice itself;  split > 1: partial[split][M][48]
+  float* out; int ldc; int N;                     // direct: the output slice itself;  else partial[piece][M][48]
   int B, H, W, TH, TW, T;                         // T = B * TH * TW tiles
-  int split;
+  int G;                                          // workgroups that own work (the grid may be larger: the surplus exits at once)
+  int gran;                                       // slabs per granule of the partition: 1 (cuts at any slab), nslab (whole tile blocks only) or `per`
+  int direct;                                     // no tile block is cut (gran == nslab): every piece is a whole block and is stored to the output itself
+  int per, span;                                  // per > 0: fixed K chunks of `per` slabs, one piece each, piece plane = chunk index; span = chunks x per
+                                                  // (a tile block's slabs padded to whole chunks).  per == 0: span = nslab, a piece ends where the range or the block ends
+  long units;                                     // tile blocks x span
   unsigned a_bytes;
 };
+
+// The static partition of the persistent walk.  The U = tile blocks x nslab (tile block, slab) units are ordered tile block major; workgroup b of G
+// owns the units [floor(b U / G), floor((b + 1) U / G)) - with G <= U never empty, balanced to +-1.  Hence unit u belongs to workgroup
+// floor(((u + 1) G - 1) / U), and the pieces of tile block t are the consecutive workgroups wino_owner(t nslab) .. wino_owner((t + 1) nslab - 1), in
+// ascending slab order: piece j of block t is plane j of the partial buffer.  Pure arithmetic on both sides (forward and reduction), no table.
+__host__ __device__ __forceinline__ int wino_owner(long u, int G, long U) { return (int)(((u + 1) * G - 1) / U); }
 
 // Wave specialisation: waves 0-3 are CONSUMERS (one per SIMD; wave w owns transform positions 4w .. 4w+3: 4 x (4 x 3) MFMA tiles = 192
 // accumulator registers, 192 MFMAs per 16-channel slab = the SIMD's matrix pipe for 6 144 cycles, next to 16 ds_read_b128 and 12 coalesced
@@ -117,87 +135,139 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, g = lane >> 4;
   const int nslab = p.C / 16;
-  int s_begin = 0, s_end = nslab;
-  if (p.split > 1) {
-    const int per = (nslab + p.split - 1) / p.split;
-    s_begin = blockIdx.y * per;
-    s_end = min(nslab, s_begin + per);
-  }
-  const int tile0 = blockIdx.x * TT;
+  // ---- the workgroup's range of (tile block, slab) units: arithmetic on blockIdx.x alone; nobody waits for anybody ----
+  if ((int)blockIdx.x >= p.G) return;                // surplus workgroups of a forced grid: gone before any barrier
+  const long ngran = p.units / p.gran;
+  long unit = (long)blockIdx.x * ngran / p.G * p.gran;
+  const long u_end = (long)(blockIdx.x + 1) * ngran / p.G * p.gran;
+  if (unit >= u_end) return;
   const bool producer = wave >= 4;
   const int pos0 = (wave & 3) * 4;
-  f32x4 acc[4][4][3];
-#pragma unroll
-  for (int pp = 0; pp < 4; ++pp)
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 3; ++nt) acc[pp][mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int tpi = p.TH * p.TW;
+  const long Mtot = (long)p.B * p.H * p.W;
 
-  if (s_begin < s_end) {
-    if (producer) {
-      // ---- producer: thread -> channel quad cq (4 consecutive channels = one 16-byte chunk of the slab) of tile tl ----
-      // Everything here competes with the partner wave's MFMAs for the SIMD's issue port (measured: the producers' vector instructions
-      // ADD to the slab time, they do not hide under the matrix pipe), so the instruction count is what is minimised: one 16-byte
-      // gather per patch position, BatchNorm + ReLU + zero padding in two instructions per element (v_fma, v_med3 against a per-position
-      // upper bound that is +inf inside the image and 0 in the padding), the two 1-D transforms in place, one 16-byte LDS store per position.
-      const int ptid = tid - 256, tl = ptid >> 2, cq = ptid & 3;
-      unsigned voff[16];
-      float hi[16];
-      {
-        const int t = tile0 + tl;
-        const bool tok = t < p.T;
-        const int tpi = p.TH * p.TW;
+  // ---- producer state: thread -> channel quad cq (4 consecutive channels = one 16-byte chunk of the slab) of tile tl ----
+  // Everything the producers do competes with the partner wave's MFMAs for the SIMD's issue port (measured: the producers' vector instructions
+  // ADD to the slab time, they do not hide under the matrix pipe), so the instruction count is what is minimised: one 16-byte
+  // gather per patch position, BatchNorm + ReLU + zero padding in two instructions per element (v_fma, v_med3 against a per-position
+  // upper bound that is +inf inside the image and 0 in the padding), the two 1-D transforms in place, one 16-byte LDS store per position.
+  const int ptid = tid & 255, tl = ptid >> 2, cq = ptid & 3;
+  unsigned voff[16];
+  float hi[16];
+  auto place = [&](int tb) {                         // the 16 gather offsets and bounds of this thread's tile in tile block tb
+    const int t = tb * TT + tl;
+    const bool tok = t < p.T;
+    const int b = t / tpi, rem = t - b * tpi;
+    const int ty = rem / p.TW, tx = rem - ty * p.TW;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int y = 2 * ty - 1 + i, x = 2 * tx - 1 + j;
+        const bool ok = tok && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+        voff[i * 4 + j] = ok ? (unsigned)((b * p.H + y) * p.W + x) * (unsigned)(p.lda * 4) + (unsigned)(cq * 16) : WOOB;
+        hi[i * 4 + j] = ok ? __builtin_inff() : 0.f;
+      }
+  };
+  const __amdgpu_buffer_rsrc_t srdA = wsrd(p.A, p.a_bytes);
+  const int slot = cq ^ swz(tl);
+  float rv[4][16];                                   // [channel][patch position]; the SLP vectoriser pairs the transform's adds into v_pk_add_f32
+                                                     // (measured 1-3 % faster than scalar adds here; s_setprio for the consumers: no effect)
+  auto load_raw = [&](int s) {
+    // the slab's channel offset travels in the scalar offset: the range check looks at the vector offset alone, where WOOB marks
+    // a padded position (a valid offset + s*64 stays inside the tensor: s*16 + 4*cq + 3 < C)
+    const int so = s * 64;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(srdA, (int)voff[q], so, 0);
+      rv[0][q] = __uint_as_float(v.x); rv[1][q] = __uint_as_float(v.y); rv[2][q] = __uint_as_float(v.z); rv[3][q] = __uint_as_float(v.w);
+    }
+  };
+  auto transform_store = [&](int s, float* Vb) {
+    if (BNRELU) {
+      const f32x4 sc = *reinterpret_cast<const f32x4*>(p.a_scale + s * 16 + cq * 4), sh = *reinterpret_cast<const f32x4*>(p.a_shift + s * 16 + cq * 4);
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) rv[c][q] = __builtin_amdgcn_fmed3f(fmaf(rv[c][q], sc[c], sh[c]), 0.f, hi[q]);
+    }
+#define RDM_WINO_1D(v, i0, i1, i2, i3)                                                        \
+    { const float d0 = v[i0], d1 = v[i1], d2 = v[i2], d3 = v[i3];                         \
+      v[i0] = d0 - d2; v[i1] = d1 + d2; v[i2] = d2 - d1; v[i3] = d1 - d3; }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) RDM_WINO_1D(rv[c], j, 4 + j, 8 + j, 12 + j)                      // B^T d: columns
+#pragma unroll
+      for (int i = 0; i < 4; ++i) RDM_WINO_1D(rv[c], 4 * i, 4 * i + 1, 4 * i + 2, 4 * i + 3)      // (.) B: rows
+    }
+#undef RDM_WINO_1D
+#pragma unroll
+    for (int pos = 0; pos < 16; ++pos)
+      *reinterpret_cast<f32x4*>(Vb + ((pos * TT + tl) * 16 + slot * 4)) = f32x4{rv[0][pos], rv[1][pos], rv[2][pos], rv[3][pos]};
+  };
+  // the piece in hand: slabs [s_begin, s_end) of tile block tb
+  const int cap = p.per > 0 ? p.per : nslab;       // slabs a piece may hold
+  int tb = (int)(unit / p.span);
+  int s_begin = (int)(unit - (long)tb * p.span);
+  int plen = (int)min((long)min(cap, p.span - s_begin), u_end - unit);      // the piece's share of the range (padded slabs)
+  int s_end = min(nslab, s_begin + plen);
+  bool more;
+  int n_tb, n_begin, n_len;
+  float* dst;
+  const int ldo = p.direct ? p.ldc : 48;
+  // end of a piece's slab loop.  The next piece of the range starts where this one ended: slab 0 of the next tile block, or (fixed chunks) the
+  // next chunk of this one.  The finished piece goes to the output slice (no block is cut) or to its plane of the partial buffer: its index among
+  // the block's pieces, i.e. the chunk index or the distance to the workgroup that owns the block's first slab.
+  auto piece_done = [&]() {
+    const int plane = p.per > 0 ? s_begin / p.per : (int)blockIdx.x - wino_owner((long)tb * nslab, p.G, p.units);
+    dst = p.direct ? p.out : p.out + (long)plane * Mtot * 48;
+    unit += plen;
+    more = unit < u_end;
+    n_tb = (int)(unit / p.span);
+    n_begin = (int)(unit - (long)n_tb * p.span);
+    n_len = (int)min((long)min(cap, p.span - n_begin), u_end - unit);
+  };
+  // ---- epilogue: M (16 positions, held by the consumers) -> LDS, two halves of 32 tiles; Y = A^T M A; store.  It reuses the V buffers: every
+  // consumer has passed the last slab's barrier (its reads retired by the lgkmcnt(0) before it), and the barrier that ends the second half keeps
+  // the producers' slab 0 of the next tile block out of the image until the last transform thread has read it.  All 8 waves transform. ----
+  float* Ms = smem;
+  auto out_transform = [&](int h) {
+#pragma unroll 1
+    for (int it = 0; it < 3; ++it) {
+      const int idx = tid + it * 512;
+      const int tl2 = idx / 48, n = idx - tl2 * 48;
+      const int t = tb * TT + h * 32 + tl2;
+      if (t < p.T && n < p.N) {
+        float m[16];
+#pragma unroll
+        for (int pos = 0; pos < 16; ++pos) m[pos] = Ms[(pos * 32 + tl2) * LDM + n];
+        float u[2][4];                                              // A^T M: rows
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { u[0][j] = m[j] + m[4 + j] + m[8 + j]; u[1][j] = m[4 + j] - m[8 + j] - m[12 + j]; }
         const int b = t / tpi, rem = t - b * tpi;
         const int ty = rem / p.TW, tx = rem - ty * p.TW;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int y = 2 * ty - 1 + i, x = 2 * tx - 1 + j;
-            const bool ok = tok && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-            voff[i * 4 + j] = ok ? (unsigned)((b * p.H + y) * p.W + x) * (unsigned)(p.lda * 4) + (unsigned)(cq * 16) : WOOB;
-            hi[i * 4 + j] = ok ? __builtin_inff() : 0.f;
+        for (int a2 = 0; a2 < 2; ++a2) {
+          const float y0 = u[a2][0] + u[a2][1] + u[a2][2], y1 = u[a2][1] - u[a2][2] - u[a2][3];
+          const int y = 2 * ty + a2, x = 2 * tx;
+          if (y < p.H) {
+            float* o = dst + ((long)(b * p.H + y) * p.W + x) * ldo + n;
+            o[0] = y0;
+            if (x + 1 < p.W) o[ldo] = y1;
           }
+        }
       }
-      const __amdgpu_buffer_rsrc_t srdA = wsrd(p.A, p.a_bytes);
-      const int slot = cq ^ swz(tl);
-      float rv[4][16];                               // [channel][patch position]; the SLP vectoriser pairs the transform's adds into v_pk_add_f32
-                                                     // (measured 1-3 % faster than scalar adds here; s_setprio for the consumers: no effect)
-      auto load_raw = [&](int s) {
-        // the slab's channel offset travels in the scalar offset: the range check looks at the vector offset alone, where WOOB marks
-        // a padded position (a valid offset + s*64 stays inside the tensor: s*16 + 4*cq + 3 < C)
-        const int so = s * 64;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(srdA, (int)voff[q], so, 0);
-          rv[0][q] = __uint_as_float(v.x); rv[1][q] = __uint_as_float(v.y); rv[2][q] = __uint_as_float(v.z); rv[3][q] = __uint_as_float(v.w);
-        }
-      };
-      auto transform_store = [&](int s, float* Vb) {
-        if (BNRELU) {
-          const f32x4 sc = *reinterpret_cast<const f32x4*>(p.a_scale + s * 16 + cq * 4), sh = *reinterpret_cast<const f32x4*>(p.a_shift + s * 16 + cq * 4);
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) rv[c][q] = __builtin_amdgcn_fmed3f(fmaf(rv[c][q], sc[c], sh[c]), 0.f, hi[q]);
-        }
-#define RDM_WINO_1D(v, i0, i1, i2, i3)                                                        \
-        { const float d0 = v[i0], d1 = v[i1], d2 = v[i2], d3 = v[i3];                         \
-          v[i0] = d0 - d2; v[i1] = d1 + d2; v[i2] = d2 - d1; v[i3] = d1 - d3; }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) RDM_WINO_1D(rv[c], j, 4 + j, 8 + j, 12 + j)                      // B^T d: columns
-#pragma unroll
-          for (int i = 0; i < 4; ++i) RDM_WINO_1D(rv[c], 4 * i, 4 * i + 1, 4 * i + 2, 4 * i + 3)      // (.) B: rows
-        }
-#undef RDM_WINO_1D
-#pragma unroll
-        for (int pos = 0; pos < 16; ++pos)
-          *reinterpret_cast<f32x4*>(Vb + ((pos * TT + tl) * 16 + slot * 4)) = f32x4{rv[0][pos], rv[1][pos], rv[2][pos], rv[3][pos]};
-      };
-      load_raw(s_begin);
+    }
+  };
+  // The two roles run their own copy of the piece loop (the accumulators live in the consumers' copy alone, the patch registers in the producers':
+  // together they would not fit the 256 registers of a wave) and meet at the same barriers: one per slab, one before and two in each half of the epilogue.
+  if (producer) {
+    place(tb);
+    load_raw(s_begin);
+#pragma unroll 1
+    for (;;) {
+      // raw(s_begin) is in flight: issued before the loop, or under the output transform of the piece before
       transform_store(s_begin, smem);
       load_raw(min(s_begin + 1, s_end - 1));
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -211,21 +281,45 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p)
         }
         __builtin_amdgcn_s_barrier();
       }
-    } else {
-      // ---- consumer: positions pos0 .. pos0 + 3 ----
-      const f32x4* Uf = reinterpret_cast<const f32x4*>(p.U) + lane;
-      auto load_b = [&](int s, int pos, f32x4 (&b)[3]) {
+      piece_done();
+      if (more) {                                                       // the next piece's first gathers land under the output transform
+        if (n_tb != tb) place(n_tb);
+        load_raw(n_begin);
+      }
+      __syncthreads();
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        __syncthreads();                                                // the consumers' half h is in the image
+        out_transform(h);
+        __syncthreads();
+      }
+      if (!more) break;
+      tb = n_tb; s_begin = n_begin; plen = n_len; s_end = min(nslab, s_begin + plen);
+    }
+  } else {
+    // ---- consumer: positions pos0 .. pos0 + 3 ----
+    const f32x4* Uf = reinterpret_cast<const f32x4*>(p.U) + lane;
+    auto load_b = [&](int s, int pos, f32x4 (&b)[3]) {
 #pragma unroll
-        for (int nt = 0; nt < 3; ++nt) b[nt] = Uf[(((long)s * 16 + pos) * 3 + nt) * 64];
-      };
-      const int aslot = (g ^ swz(l16)) * 4;
-      // Software pipeline, pinned with sched_barrier (left alone, hipcc sinks every load next to its first use and the matrix pipe waits
-      // for L2): the B fragments of position pp+1 (three 1-KiB loads) are issued before the 48 MFMAs of position pp, the A fragment of
-      // M-tile mt+1 (one ds_read_b128) before the 12 MFMAs of M-tile mt.  MFMA order mt -> e -> nt: an accumulator is revisited after 3
-      // MFMAs (96 cycles > the 40-cycle dependent latency).
-      f32x4 bq[2][3], aq[2];
-      auto load_a1 = [&](const float* Vb, int pos, int mt) { return *reinterpret_cast<const f32x4*>(Vb + ((pos * TT + mt * 16 + l16) * 16 + aslot)); };
+      for (int nt = 0; nt < 3; ++nt) b[nt] = Uf[(((long)s * 16 + pos) * 3 + nt) * 64];
+    };
+    const int aslot = (g ^ swz(l16)) * 4;
+    // Software pipeline, pinned with sched_barrier (left alone, hipcc sinks every load next to its first use and the matrix pipe waits
+    // for L2): the B fragments of position pp+1 (three 1-KiB loads) are issued before the 48 MFMAs of position pp, the A fragment of
+    // M-tile mt+1 (one ds_read_b128) before the 12 MFMAs of M-tile mt.  MFMA order mt -> e -> nt: an accumulator is revisited after 3
+    // MFMAs (96 cycles > the 40-cycle dependent latency).
+    f32x4 bq[2][3], aq[2];
+    auto load_a1 = [&](const float* Vb, int pos, int mt) { return *reinterpret_cast<const f32x4*>(Vb + ((pos * TT + mt * 16 + l16) * 16 + aslot)); };
+#pragma unroll 1
+    for (;;) {
+      f32x4 acc[4][4][3];
       load_b(s_begin, pos0, bq[0]);
+#pragma unroll
+      for (int pp = 0; pp < 4; ++pp)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < 3; ++nt) acc[pp][mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       for (int s = s_begin; s < s_end; ++s) {
@@ -253,57 +347,26 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino_fwd_kernel(WinoFwdArgs p)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
-    }
-  }
-  __syncthreads();
-
-  // ---- epilogue: M (16 positions, held by the consumers) -> LDS, two halves of 32 tiles; Y = A^T M A; store ----
-  float* Ms = smem;
-  const long Mtot = (long)p.B * p.H * p.W;
-  float* dst = p.split > 1 ? p.out + (long)blockIdx.y * Mtot * 48 : p.out;
-  const int ldo = p.split > 1 ? 48 : p.ldc;
-  const int tpi = p.TH * p.TW;
+      piece_done();
+      __syncthreads();
 #pragma unroll 1
-  for (int h = 0; h < 2; ++h) {
-    if (!producer) {
+      for (int h = 0; h < 2; ++h) {
 #pragma unroll
-      for (int pp = 0; pp < 4; ++pp)
+        for (int pp = 0; pp < 4; ++pp)
 #pragma unroll
-        for (int mtl = 0; mtl < 2; ++mtl)
+          for (int mtl = 0; mtl < 2; ++mtl)
 #pragma unroll
-          for (int nt = 0; nt < 3; ++nt)
+            for (int nt = 0; nt < 3; ++nt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              Ms[((pos0 + pp) * 32 + mtl * 16 + 4 * g + r) * LDM + nt * 16 + l16] = h == 0 ? acc[pp][mtl][nt][r] : acc[pp][2 + mtl][nt][r];
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int it = 0; it < 3; ++it) {
-      const int idx = tid + it * 512;
-      const int tl2 = idx / 48, n = idx - tl2 * 48;
-      const int t = tile0 + h * 32 + tl2;
-      if (t < p.T && n < p.N) {
-        float m[16];
-#pragma unroll
-        for (int pos = 0; pos < 16; ++pos) m[pos] = Ms[(pos * 32 + tl2) * LDM + n];
-        float u[2][4];                                              // A^T M: rows
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { u[0][j] = m[j] + m[4 + j] + m[8 + j]; u[1][j] = m[4 + j] - m[8 + j] - m[12 + j]; }
-        const int b = t / tpi, rem = t - b * tpi;
-        const int ty = rem / p.TW, tx = rem - ty * p.TW;
-#pragma unroll
-        for (int a2 = 0; a2 < 2; ++a2) {
-          const float y0 = u[a2][0] + u[a2][1] + u[a2][2], y1 = u[a2][1] - u[a2][2] - u[a2][3];
-          const int y = 2 * ty + a2, x = 2 * tx;
-          if (y < p.H) {
-            float* o = dst + ((long)(b * p.H + y) * p.W + x) * ldo + n;
-            o[0] = y0;
-            if (x + 1 < p.W) o[ldo] = y1;
-          }
-        }
+              for (int r = 0; r < 4; ++r)
+                Ms[((pos0 + pp) * 32 + mtl * 16 + 4 * g + r) * LDM + nt * 16 + l16] = h == 0 ? acc[pp][mtl][nt][r] : acc[pp][2 + mtl][nt][r];
+        __syncthreads();
+        out_transform(h);
+        __syncthreads();
       }
+      if (!more) break;
+      tb = n_tb; s_begin = n_begin; plen = n_len; s_end = min(nslab, s_begin + plen);
     }
-    __syncthreads();
   }
 }
 
@@ -337,6 +400,51 @@ __global__ __launch_bounds__(256) void k_wino_reduce(const float* __restrict__ p
     for (int r = 0; r < 21; ++r) { a += red0[r][threadIdx.x]; b += red1[r][threadIdx.x]; }
     atomicAdd(stat0 + threadIdx.x, a);
     atomicAdd(stat1 + threadIdx.x, b);
+  }
+}
+
+// The same for the persistent f32 forward, whose tile blocks are cut into a VARIABLE number of pieces (planes 0 .. pieces - 1 of partial[plane][M][48],
+// ascending slab order): the count comes from the partition arithmetic (wino_owner), per workgroup.  A workgroup owns one output row (a2) of 32 tiles
+// of a tile block; a thread = (tile, x parity, float4 column) walks 4 tiles - 24 consecutive threads cover the 384 contiguous bytes of a tile's two pixels.
+struct WinoReduceArgs {
+  const float* part; long M; int N; float* out; int ldc; double* stat0; double* stat1;
+  int H, W, TH, TW, T, nslab, G; long units;
+};
+__global__ __launch_bounds__(192) void k_wino_reduce_pieces(WinoReduceArgs p) {
+  const int tb = blockIdx.x >> 2, a2 = (blockIdx.x >> 1) & 1, half = blockIdx.x & 1;
+  const int first = wino_owner((long)tb * p.nslab, p.G, p.units);
+  const int pieces = wino_owner((long)(tb + 1) * p.nslab - 1, p.G, p.units) - first + 1;
+  const int n4 = threadIdx.x % 12, xpar = (threadIdx.x / 12) & 1, tr = threadIdx.x / 24;      // 8 tiles per pass
+  const int tpi = p.TH * p.TW;
+  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int t = tb * TT + half * 32 + it * 8 + tr;
+    if (t >= p.T) continue;
+    const int b = t / tpi, rem = t - b * tpi;
+    const int ty = rem / p.TW, tx = rem - ty * p.TW;
+    const int y = 2 * ty + a2, x = 2 * tx + xpar;
+    if (y >= p.H || x >= p.W) continue;
+    const long m = (long)(b * p.H + y) * p.W + x;
+    f32x4 v = *reinterpret_cast<const f32x4*>(p.part + m * 48 + n4 * 4);
+    for (int j = 1; j < pieces; ++j) v += *reinterpret_cast<const f32x4*>(p.part + ((long)j * p.M + m) * 48 + n4 * 4);
+    float* o = p.out + m * p.ldc + n4 * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (n4 * 4 + e < p.N) o[e] = v[e];
+    s0 += v; s1 += v * v;
+  }
+  if (p.stat0 == nullptr) return;
+  __shared__ float red0[16][48], red1[16][48];                      // block reduction: 16 (tile, x parity) lanes -> 1
+  const int rl = threadIdx.x / 12;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { red0[rl][n4 * 4 + e] = s0[e]; red1[rl][n4 * 4 + e] = s1[e]; }
+  __syncthreads();
+  if (threadIdx.x < 48 && (int)threadIdx.x < p.N) {
+    double a = 0, b = 0;
+    for (int r = 0; r < 16; ++r) { a += red0[r][threadIdx.x]; b += red1[r][threadIdx.x]; }
+    atomicAdd(p.stat0 + threadIdx.x, a);
+    atomicAdd(p.stat1 + threadIdx.x, b);
   }
 }
 
@@ -976,6 +1084,86 @@ static int wino_fwd_finish(const WinoConv& a, int split, long M, hipStream_t s) 
   return 0;
 }
 
+// ---- the f32 forward: a persistent walk over (tile block, slab) units ----
+// One workgroup is resident per CU (128 KB of LDS), so G = the chip's 256 workgroup slots, each with a contiguous range of the units - but never
+// fewer than 4 slabs per workgroup (the K split's old floor: below that the prologue / epilogue outweighs the slabs).  `forced` (WinoConv::split)
+// sets G from outside; above the unit count the surplus workgroups own nothing.
+constexpr int WINO_SLOTS = 256;
+static int wino_groups(long tblocks, int nslab, int forced) {
+  const long U = tblocks * nslab;
+  const long G = forced > 0 ? forced : std::min<long>(WINO_SLOTS, std::max<long>(1, U / 4));
+  return (int)std::min(G, U);
+}
+// Planes of the partial buffer: a workgroup holds >= q = floor(U / G) units, a tile block is nslab consecutive units, so all but the first and last
+// of its pieces are whole ranges:  pieces <= ceil(nslab / q) + 1  (and <= nslab, <= G).  1: no block is ever cut, no partial.
+static int wino_walk_planes(int T, int nslab, int groups) {
+  const long tblocks = cdiv(T, TT);
+  const int G = wino_groups(tblocks, nslab, groups);
+  if (G == 1 || nslab == 1) return 1;
+  const long q = tblocks * nslab / G;
+  return (int)std::min<long>(std::min(nslab, G), (nslab + q - 1) / q + 1);
+}
+// what a caller sizes `partial` by: the walk's planes, and for the launcher's own choice also the fixed K chunks of the deterministic mode
+int wino_fwd_planes(int T, int nslab, int groups) {
+  const int w = wino_walk_planes(T, nslab, groups);
+  return groups > 0 ? w : std::max(w, wino_pick_split(T, nslab, false));
+}
+
+static int launch_wino_fwd_persistent(const WinoConv& a, int TH, int TW, int T, unsigned a_bytes, hipStream_t s) {
+  const long M = (long)a.B * a.H * a.W;
+  const int nslab = a.C / 16;
+  const long tblocks = cdiv(T, TT);
+  RDM_CHECK_ARG(a.split >= 0 && a.split <= 65535, "winograd 3x3: forced workgroup count (%d) out of range", a.split);
+  if (t_deterministic && a.split == 0) {
+    // Deterministic mode promises the SAME bits from build to build, not only from run to run (recorded gradient and logits hashes), and the bits
+    // depend on where the slab sum is cut: so here the pieces are the fixed K chunks of wino_pick_split - the same walk, but a range is dealt in
+    // whole chunks, a chunk is never merged with its neighbour, and chunk c of every tile block is plane c for the ordered k_wino_reduce.
+    int split = wino_pick_split(T, nslab, false);
+    if (split > 1 && a.partial == nullptr) split = 1;
+    if (split > 1 && a.partial_floats < (size_t)split * M * 48) split = std::max<long>(1, (long)(a.partial_floats / ((size_t)M * 48)));
+    const int per = (nslab + split - 1) / split, nchunk = (nslab + per - 1) / per;
+    WinoFwdArgs k{};
+    k.A = a.A; k.lda = a.lda; k.C = a.C; k.a_scale = a.a_scale; k.a_shift = a.a_shift; k.U = a.U;
+    k.out = nchunk > 1 ? a.partial : a.out; k.ldc = a.ldc; k.N = a.N;
+    k.B = a.B; k.H = a.H; k.W = a.W; k.TH = TH; k.TW = TW; k.T = T; k.a_bytes = a_bytes;
+    k.per = per; k.span = nchunk * per; k.gran = per; k.units = tblocks * k.span; k.direct = nchunk == 1;
+    k.G = (int)std::min<long>(WINO_SLOTS, tblocks * nchunk);
+    void* prof = profile_begin(s, 2.0 * M * a.N * 9.0 * a.C, 9);
+    RDM_CENSUS("conv3x3_wino_fwd_kernel/%s/%s", a.a_scale ? "bn1" : "bn0", nchunk > 1 ? "PARTIAL" : (a.stat0 ? "STORE+stats" : "STORE"));
+    if (a.a_scale) hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<true>), dim3((unsigned)k.G), dim3(512), 0, s, k);
+    else hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<false>), dim3((unsigned)k.G), dim3(512), 0, s, k);
+    profile_end(prof, s);
+    RDM_LAUNCH_OK();
+    return wino_fwd_finish(a, nchunk, M, s);
+  }
+  const int planes = wino_walk_planes(T, nslab, a.split);
+  // no block is cut, or nowhere to put the pieces: whole tile blocks per workgroup, stored to the output slice itself
+  const bool direct = planes == 1 || a.partial == nullptr || a.partial_floats < (size_t)planes * M * 48;
+  WinoFwdArgs k{};
+  k.A = a.A; k.lda = a.lda; k.C = a.C; k.a_scale = a.a_scale; k.a_shift = a.a_shift; k.U = a.U;
+  k.out = direct ? a.out : a.partial; k.ldc = a.ldc; k.N = a.N;
+  k.B = a.B; k.H = a.H; k.W = a.W; k.TH = TH; k.TW = TW; k.T = T; k.a_bytes = a_bytes;
+  k.units = tblocks * nslab; k.span = nslab; k.per = 0; k.direct = direct; k.gran = direct ? nslab : 1;
+  k.G = wino_groups(tblocks, nslab, a.split);
+  if (direct) k.G = (int)std::min<long>(k.G, tblocks);
+  void* prof = profile_begin(s, 2.0 * M * a.N * 9.0 * a.C, 9);
+  RDM_CENSUS("conv3x3_wino_fwd_kernel/%s/%s", a.a_scale ? "bn1" : "bn0", !direct ? "PARTIAL" : (a.stat0 ? "STORE+stats" : "STORE"));
+  dim3 grid((unsigned)std::max(k.G, a.split));
+  if (a.a_scale) hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<true>), grid, dim3(512), 0, s, k);
+  else hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<false>), grid, dim3(512), 0, s, k);
+  profile_end(prof, s);
+  RDM_LAUNCH_OK();
+  // every block goes through the ordered reduction (statistics taken exactly once, there); deterministic mode and the direct form: the column pass
+  const bool stats_apart = a.stat0 && (direct || t_deterministic);
+  if (!direct) {
+    WinoReduceArgs r{a.partial, M, a.N, a.out, a.ldc, stats_apart ? nullptr : a.stat0, stats_apart ? nullptr : a.stat1, a.H, a.W, TH, TW, T, nslab, k.G, k.units};
+    hipLaunchKernelGGL(k_wino_reduce_pieces, dim3((unsigned)(tblocks * 4)), dim3(192), 0, s, r);
+    RDM_LAUNCH_OK();
+  }
+  if (stats_apart) return launch_colstats(a.out, a.ldc, (int)M, a.N, a.stat0, a.stat1, s);
+  return 0;
+}
+
 int launch_conv3x3_wino_fwd(const WinoConv& a, hipStream_t s) {
   RDM_CHECK_ARG(a.C % 16 == 0 && a.C > 0 && a.N >= 1 && a.N <= 48, "winograd 3x3: C (%d) must be a multiple of 16, N (%d) <= 48", a.C, a.N);
   RDM_CHECK_ARG(a.lda % 4 == 0 && ((uintptr_t)a.A & 15) == 0, "winograd 3x3: input stride must be a multiple of 4 floats and the tensor 16-byte aligned");
@@ -985,37 +1173,24 @@ int launch_conv3x3_wino_fwd(const WinoConv& a, hipStream_t s) {
   if (ab >= 0xFFFFFFFFL) { set_error("winograd 3x3: operand extent >= 4 GiB is not supported by the 32-bit buffer addressing"); return RDM_ERR_UNSUPPORTED; }
   const int TH = (a.H + 1) / 2, TW = (a.W + 1) / 2;
   const int T = a.B * TH * TW, nslab = a.C / 16;
-  int split = a.split > 0 ? std::min(a.split, nslab) : wino_pick_split(T, nslab, a.x6 != 0);
+  if (!a.x6) return launch_wino_fwd_persistent(a, TH, TW, T, (unsigned)ab, s);
+  int split = a.split > 0 ? std::min(a.split, nslab) : wino_pick_split(T, nslab, true);
   if (split > 1 && a.partial == nullptr) split = 1;
   if (split > 1 && a.partial_floats < (size_t)split * M * 48) split = std::max<long>(1, (long)(a.partial_floats / ((size_t)M * 48)));
-  if (a.x6) {
-    WinoX6Args k{};
-    k.A = a.A; k.lda = a.lda; k.C = a.C; k.a_scale = a.a_scale; k.a_shift = a.a_shift; k.U = reinterpret_cast<const unsigned char*>(a.U);
-    k.out = split > 1 ? a.partial : a.out; k.ldc = a.ldc; k.N = a.N;
-    k.B = a.B; k.H = a.H; k.W = a.W; k.TH = TH; k.TW = TW; k.T = T; k.split = split; k.a_bytes = (unsigned)ab; k.u_bytes = (unsigned)wino_u_bytes(a.C, true);
-    void* prof = profile_begin(s, 2.0 * M * a.N * 9.0 * a.C, 18);
-    RDM_CENSUS("conv3x3_wino_x6_kernel/%s/%s", a.a_scale ? "bn1" : "bn0", split > 1 ? "PARTIAL" : (a.stat0 ? "STORE+stats" : "STORE"));
-    dim3 grid((unsigned)cdiv(T, TX), (unsigned)split);
-    if (a.a_scale) {
-      RDM_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_x6_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * XIMG));
-      hipLaunchKernelGGL((conv3x3_wino_x6_kernel<true>), grid, dim3(448), 2 * XIMG, s, k);
-    } else {
-      RDM_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_x6_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * XIMG));
-      hipLaunchKernelGGL((conv3x3_wino_x6_kernel<false>), grid, dim3(448), 2 * XIMG, s, k);
-    }
-    profile_end(prof, s);
-    RDM_LAUNCH_OK();
-    return wino_fwd_finish(a, split, M, s);
-  }
-  WinoFwdArgs k{};
-  k.A = a.A; k.lda = a.lda; k.C = a.C; k.a_scale = a.a_scale; k.a_shift = a.a_shift; k.U = a.U;
+  WinoX6Args k{};
+  k.A = a.A; k.lda = a.lda; k.C = a.C; k.a_scale = a.a_scale; k.a_shift = a.a_shift; k.U = reinterpret_cast<const unsigned char*>(a.U);
   k.out = split > 1 ? a.partial : a.out; k.ldc = a.ldc; k.N = a.N;
-  k.B = a.B; k.H = a.H; k.W = a.W; k.TH = TH; k.TW = TW; k.T = T; k.split = split; k.a_bytes = (unsigned)ab;
-  void* prof = profile_begin(s, 2.0 * M * a.N * 9.0 * a.C, 9);
-  RDM_CENSUS("conv3x3_wino_fwd_kernel/%s/%s", a.a_scale ? "bn1" : "bn0", split > 1 ? "PARTIAL" : (a.stat0 ? "STORE+stats" : "STORE"));
-  dim3 grid((unsigned)cdiv(T, TT), (unsigned)split);
-  if (a.a_scale) hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<true>), grid, dim3(512), 0, s, k);
-  else hipLaunchKernelGGL((conv3x3_wino_fwd_kernel<false>), grid, dim3(512), 0, s, k);
+  k.B = a.B; k.H = a.H; k.W = a.W; k.TH = TH; k.TW = TW; k.T = T; k.split = split; k.a_bytes = (unsigned)ab; k.u_bytes = (unsigned)wino_u_bytes(a.C, true);
+  void* prof = profile_begin(s, 2.0 * M * a.N * 9.0 * a.C, 18);
+  RDM_CENSUS("conv3x3_wino_x6_kernel/%s/%s", a.a_scale ? "bn1" : "bn0", split > 1 ? "PARTIAL" : (a.stat0 ? "STORE+stats" : "STORE"));
+  dim3 grid((unsigned)cdiv(T, TX), (unsigned)split);
+  if (a.a_scale) {
+    RDM_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_x6_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * XIMG));
+    hipLaunchKernelGGL((conv3x3_wino_x6_kernel<true>), grid, dim3(448), 2 * XIMG, s, k);
+  } else {
+    RDM_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_x6_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * XIMG));
+    hipLaunchKernelGGL((conv3x3_wino_x6_kernel<false>), grid, dim3(448), 2 * XIMG, s, k);
+  }
   profile_end(prof, s);
   RDM_LAUNCH_OK();
   return wino_fwd_finish(a, split, M, s);
