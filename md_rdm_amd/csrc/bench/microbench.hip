@@ -8,14 +8,10 @@
 
 namespace rdm {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// (the host pass of hipcc cannot type-check the gfx950-only builtin and silently drops the kernel's host stub if it sees it)
-// XCD-aware block order (igemm.hip xcd_block_order), optionally in row groups of G tiles walked column by column
+// XCD-aware block order (dev_prims.h: xcd_logical; igemm.hip xcd_block_order), optionally in row groups of G tiles walked column by column
 __device__ __forceinline__ void tile_order(int G, int& bx, int& by) {
   const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy, L = blockIdx.x + gx * blockIdx.y;
-  const unsigned x = L & 7u, seq = L >> 3, q = total >> 3, r = total & 7u;
-  const unsigned Lp = x * q + (x < r ? x : r) + seq;
+  const unsigned Lp = xcd_logical(L, total);
   if (G >= 2) {
     const unsigned gsz = (unsigned)G * gx, grp = Lp / gsz, rem = Lp - grp * gsz, rows = min((unsigned)G, gy - grp * (unsigned)G), c = rem / rows;
     bx = (int)c; by = (int)(grp * G + (rem - c * rows));
@@ -23,13 +19,9 @@ __device__ __forceinline__ void tile_order(int G, int& bx, int& by) {
   }
   bx = (int)(Lp % gx); by = (int)(Lp / gx);
 }
-__device__ __forceinline__ void lds_dma16_buf(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float* lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, (int)voff, (int)soff, 0, 0);
-#endif
-}
-__device__ __forceinline__ void lds_dma16(const float* gsrc, float* lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
+// the flat-address form of dev_prims.h lds_dma16, for the experiment that compares the two
+__device__ __forceinline__ void lds_dma16_flat(const float* gsrc, float* lds_dst) {
+#if defined(__HIP_DEVICE_COMPILE__)      // (the host pass of hipcc cannot type-check the gfx950-only builtin and silently drops the kernel's host stub if it sees it)
   __builtin_amdgcn_global_load_lds(gsrc, lds_dst, 16, 0, 0);
 #endif
 }
@@ -87,8 +79,8 @@ __global__ __launch_bounds__(256, 4) void k_gemm_dma_f32(const float* A, int lda
   const int prow = lane >> 2, pch = (lane & 3) ^ ((prow >> 2) & 3);
   // buffer form (SRD + one 32-bit offset register per piece, the slab advance in a scalar offset): the flat form's 64-bit address
   // arithmetic per DMA cost 28 % of the MFMA rate in k_mfma_loop_tile (112 vs 144 TFLOP/s)
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, (int)(((long)(M - 1) * lda + K) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wt), 0, (int)(((long)(N - 1) * ldw + K) * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = make_srd(A, (unsigned)(((long)(M - 1) * lda + K) * 4));
+  const __amdgpu_buffer_rsrc_t rw = make_srd(Wt, (unsigned)(((long)(N - 1) * ldw + K) * 4));
   unsigned aoff[(AI + 3) / 4], boff[(BI + 3) / 4];
 #pragma unroll
   for (int t = 0; t < (AI + 3) / 4; ++t) aoff[t] = (unsigned)(min(m0 + (wave + 4 * t) * 16 + prow, M - 1) * lda + pch * 4) * 4u;
@@ -98,12 +90,12 @@ __global__ __launch_bounds__(256, 4) void k_gemm_dma_f32(const float* A, int lda
 #pragma unroll
     for (int t = 0; t < (AI + 3) / 4; ++t) {
       const int piece = wave + 4 * t;
-      if (piece < AI) lds_dma16_buf(ra, aoff[t], (unsigned)k0 * 4u, As(buf) + piece * 256);
+      if (piece < AI) lds_dma16(ra, aoff[t], (unsigned)k0 * 4u, As(buf) + piece * 256);
     }
 #pragma unroll
     for (int t = 0; t < (BI + 3) / 4; ++t) {
       const int piece = wave + 4 * t;
-      if (piece < BI) lds_dma16_buf(rw, boff[t], (unsigned)k0 * 4u, Bs(buf) + piece * 256);
+      if (piece < BI) lds_dma16(rw, boff[t], (unsigned)k0 * 4u, Bs(buf) + piece * 256);
     }
   };
   f32x4 acc[MT][NT];
@@ -169,8 +161,8 @@ __global__ __launch_bounds__(256, MINB) void k_gemm_dma_big_f32(const float* A, 
   tile_order(grp, bx, by);
   const int n0 = bx * BN, m0 = by * BM;
   const int prow = lane >> 2, pch = (lane & 3) ^ ((prow >> 2) & 3);
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, (int)(((long)(M - 1) * lda + K) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wt), 0, (int)(((long)(N - 1) * ldw + K) * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = make_srd(A, (unsigned)(((long)(M - 1) * lda + K) * 4));
+  const __amdgpu_buffer_rsrc_t rw = make_srd(Wt, (unsigned)(((long)(N - 1) * ldw + K) * 4));
   unsigned aoff[NA], boff[NB];
 #pragma unroll
   for (int t = 0; t < NA; ++t) aoff[t] = (unsigned)(min(m0 + (wave + 4 * t) * 16 + prow, M - 1) * lda + pch * 4) * 4u;
@@ -178,9 +170,9 @@ __global__ __launch_bounds__(256, MINB) void k_gemm_dma_big_f32(const float* A, 
   for (int t = 0; t < NB; ++t) boff[t] = (unsigned)(min(n0 + (wave + 4 * t) * 16 + prow, N - 1) * ldw + pch * 4) * 4u;
   auto issue = [&](int buf, int k0) {
 #pragma unroll
-    for (int t = 0; t < NA; ++t) lds_dma16_buf(ra, aoff[t], (unsigned)k0 * 4u, As(buf) + (wave + 4 * t) * 256);
+    for (int t = 0; t < NA; ++t) lds_dma16(ra, aoff[t], (unsigned)k0 * 4u, As(buf) + (wave + 4 * t) * 256);
 #pragma unroll
-    for (int t = 0; t < NB; ++t) lds_dma16_buf(rw, boff[t], (unsigned)k0 * 4u, Bs(buf) + (wave + 4 * t) * 256);
+    for (int t = 0; t < NB; ++t) lds_dma16(rw, boff[t], (unsigned)k0 * 4u, Bs(buf) + (wave + 4 * t) * 256);
   };
   f32x4 acc[MT][NT];
 #pragma unroll
@@ -248,8 +240,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_dma32_f32(const float* A, int l
   const int n0 = bx * BN, m0 = by * BM;
   // piece p = rows 8p .. 8p+7; lane -> (row 8p + lane/8, slot lane%8); slot c of row r holds logical chunk c ^ ((r >> 1) & 7)
   const int prow = lane >> 3;
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, (int)(((long)(M - 1) * lda + K) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wt), 0, (int)(((long)(N - 1) * ldw + K) * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = make_srd(A, (unsigned)(((long)(M - 1) * lda + K) * 4));
+  const __amdgpu_buffer_rsrc_t rw = make_srd(Wt, (unsigned)(((long)(N - 1) * ldw + K) * 4));
   unsigned aoff[NA], boff[NB];
 #pragma unroll
   for (int t = 0; t < NA; ++t) {
@@ -263,9 +255,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_dma32_f32(const float* A, int l
   }
   auto issue = [&](int buf, int k0) {
 #pragma unroll
-    for (int t = 0; t < NA; ++t) lds_dma16_buf(ra, aoff[t], (unsigned)k0 * 4u, As(buf) + (wave + 4 * t) * 256);
+    for (int t = 0; t < NA; ++t) lds_dma16(ra, aoff[t], (unsigned)k0 * 4u, As(buf) + (wave + 4 * t) * 256);
 #pragma unroll
-    for (int t = 0; t < NB; ++t) lds_dma16_buf(rw, boff[t], (unsigned)k0 * 4u, Bs(buf) + (wave + 4 * t) * 256);
+    for (int t = 0; t < NB; ++t) lds_dma16(rw, boff[t], (unsigned)k0 * 4u, Bs(buf) + (wave + 4 * t) * 256);
   };
   f32x4 acc[MT][NT];
 #pragma unroll
@@ -331,14 +323,14 @@ __global__ __launch_bounds__(256, 2) void k_gemm_dma32_tiled_f32(const float* At
   tile_order(grp, bx, by);
   const int n0 = bx * BN, m0 = by * BM;
   const int nk = K / BK;
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(At), 0, 0x7FFFFFFF, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wt), 0, 0x7FFFFFFF, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = make_srd(At, 0x7FFFFFFFu);
+  const __amdgpu_buffer_rsrc_t rw = make_srd(Wt, 0x7FFFFFFFu);
   const unsigned abase = (unsigned)by * (unsigned)nk * (BM * BK * 4u), wbase = (unsigned)bx * (unsigned)nk * (BN * BK * 4u);
   auto issue = [&](int buf, int s) {
 #pragma unroll
-    for (int t = 0; t < NA; ++t) lds_dma16_buf(ra, (unsigned)((wave + 4 * t) * 1024 + lane * 16), abase + (unsigned)s * (BM * BK * 4u), As(buf) + (wave + 4 * t) * 256);
+    for (int t = 0; t < NA; ++t) lds_dma16(ra, (unsigned)((wave + 4 * t) * 1024 + lane * 16), abase + (unsigned)s * (BM * BK * 4u), As(buf) + (wave + 4 * t) * 256);
 #pragma unroll
-    for (int t = 0; t < NB; ++t) lds_dma16_buf(rw, (unsigned)((wave + 4 * t) * 1024 + lane * 16), wbase + (unsigned)s * (BN * BK * 4u), Bs(buf) + (wave + 4 * t) * 256);
+    for (int t = 0; t < NB; ++t) lds_dma16(rw, (unsigned)((wave + 4 * t) * 1024 + lane * 16), wbase + (unsigned)s * (BN * BK * 4u), Bs(buf) + (wave + 4 * t) * 256);
   };
   f32x4 acc[MT][NT];
 #pragma unroll
@@ -502,13 +494,13 @@ __global__ __launch_bounds__(256, 4) void k_mfma_loop_tile(float* out, int iters
         float* nb6 = smem + (buf ^ 1) * (128 + 96) * 16;
         // source: a window of (span_mask + 1) floats walked in 16 KB steps, a different phase per workgroup - span 64 KB: L1-resident,
         // a few MB: L2-resident, hundreds of MB: Infinity Cache / HBM (every step reads 14 KB like a real 128 x 96 x 16 slab)
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), 0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = make_srd(src, 0x7FFFFFFFu);
         const unsigned vo = (unsigned)((wave * 1024 + lane * 4) * 4);
         const unsigned so = (((unsigned)blockIdx.x * 40503u + (unsigned)it) * 4096u & span_mask) * 4u;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) lds_dma16_buf(rs, vo, so + (unsigned)(t * 256 * 4), nb6 + (wave + 4 * t) * 256);
-        lds_dma16_buf(rs, vo, so + 128 * 4, nb6 + 128 * 16 + wave * 256);
-        if (wave < 2) lds_dma16_buf(rs, vo, so + 64 * 4, nb6 + 128 * 16 + (4 + wave) * 256);
+        for (int t = 0; t < 2; ++t) lds_dma16(rs, vo, so + (unsigned)(t * 256 * 4), nb6 + (wave + 4 * t) * 256);
+        lds_dma16(rs, vo, so + 128 * 4, nb6 + 128 * 16 + wave * 256);
+        if (wave < 2) lds_dma16(rs, vo, so + 64 * 4, nb6 + 128 * 16 + (4 + wave) * 256);
       } else {
       if (MODE != 5) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // 5: never wait for the DMA (timing only: what is ISSUING it worth?)
       else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
@@ -516,10 +508,10 @@ __global__ __launch_bounds__(256, 4) void k_mfma_loop_tile(float* out, int iters
       asm volatile("" ::: "memory");
       float* nb = smem + (buf ^ 1) * (128 + 96) * 16;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) lds_dma16(gsrc + t * 256 + (it & 7) * 512, nb + (wave + 4 * t) * 256);
+      for (int t = 0; t < 2; ++t) lds_dma16_flat(gsrc + t * 256 + (it & 7) * 512, nb + (wave + 4 * t) * 256);
       if (MODE != 4) {                                                          // 4: the A tile only (8 of the 14 KB)
-        lds_dma16(gsrc + 128, nb + 128 * 16 + wave * 256);
-        if (wave < 2) lds_dma16(gsrc + 64, nb + 128 * 16 + (4 + wave) * 256);
+        lds_dma16_flat(gsrc + 128, nb + 128 * 16 + wave * 256);
+        if (wave < 2) lds_dma16_flat(gsrc + 64, nb + 128 * 16 + (4 + wave) * 256);
       }
       }
     } else if (MODE == 2) {

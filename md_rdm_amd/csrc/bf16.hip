@@ -26,29 +26,6 @@
 
 namespace rdm {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0xFFFFFFFFu;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t srd(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint4 bld(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ float4 bldf(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  const bf16x2 r = {(__bf16)a, (__bf16)b};                  // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
-  return __builtin_bit_cast(unsigned, r);
-}
 __device__ __forceinline__ unsigned bnrelu2(unsigned u, float s0, float s1, float t0, float t1) {
   return pack2(fmaxf(fmaf(bf_lo(u), s0, t0), 0.f), fmaxf(fmaf(bf_hi(u), s1, t1), 0.f));
 }
@@ -61,11 +38,9 @@ __device__ __forceinline__ uint4 bnrelu8(uint4 v, float4 sa, float4 sb, float4 t
   return v;
 }
 
-__device__ __forceinline__ void xcd_order(int& bx, int& by) {      // see igemm.hip xcd_block_order
+__device__ __forceinline__ void xcd_order(int& bx, int& by) {      // XCD-aware block order (dev_prims.h: xcd_logical) over a 2-D grid
   const unsigned gx = gridDim.x, total = gx * gridDim.y;
-  const unsigned L = blockIdx.x + gx * blockIdx.y;
-  const unsigned x = L & 7u, seq = L >> 3, q = total >> 3, r = total & 7u;
-  const unsigned Lp = x * q + (x < r ? x : r) + seq;
+  const unsigned Lp = xcd_logical(blockIdx.x + gx * blockIdx.y, total);
   bx = (int)(Lp % gx); by = (int)(Lp / gx);
 }
 
@@ -108,8 +83,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBf16Args p) {
   int bx, by;
   xcd_order(bx, by);
   const int n0 = bx * BN, m0 = by * BM;
-  const __amdgpu_buffer_rsrc_t srdX = srd(p.X, p.x_bytes), srdW = srd(p.W, p.w_bytes);
-  const __amdgpu_buffer_rsrc_t srdS = srd(p.scale, p.p_bytes), srdT = srd(p.shift, p.p_bytes);
+  const __amdgpu_buffer_rsrc_t srdX = make_srd(p.X, p.x_bytes), srdW = make_srd(p.W, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t srdS = make_srd(p.scale, p.p_bytes), srdT = make_srd(p.shift, p.p_bytes);
   const bool bnrelu = p.scale != nullptr;
 
   const int ch = tid % CH, r0 = tid / CH;                             // this thread's chunk column and first row
@@ -135,13 +110,13 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBf16Args p) {
     const bool kok = k0 < p.K;                                        // K is a multiple of 8: a chunk is all in or all out
     const unsigned kb = (unsigned)(kt * BK * 2);
 #pragma unroll
-    for (int i = 0; i < XL; ++i) S.rx[i] = bld(srdX, (kok && xoff[i] != OOB) ? xoff[i] + kb : OOB);
+    for (int i = 0; i < XL; ++i) S.rx[i] = bld_u4(srdX, (kok && xoff[i] != OOB) ? xoff[i] + kb : OOB);
 #pragma unroll
-    for (int i = 0; i < WL; ++i) S.rw[i] = bld(srdW, (kok && woff[i] != OOB) ? woff[i] + kb : OOB);
+    for (int i = 0; i < WL; ++i) S.rw[i] = bld_u4(srdW, (kok && woff[i] != OOB) ? woff[i] + kb : OOB);
     if (bnrelu) {
       const unsigned po = kok ? (unsigned)(k0 * 4) : OOB;
-      S.sa = bldf(srdS, po); S.sb = bldf(srdS, po == OOB ? OOB : po + 16);
-      S.ta = bldf(srdT, po); S.tb = bldf(srdT, po == OOB ? OOB : po + 16);
+      S.sa = bld_f4(srdS, po); S.sb = bld_f4(srdS, po == OOB ? OOB : po + 16);
+      S.ta = bld_f4(srdT, po); S.tb = bld_f4(srdT, po == OOB ? OOB : po + 16);
     }
   };
   auto store_step = [&](int buf, const Stage& S) {
@@ -271,13 +246,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBf16Args p) {
   }
 }
 
-// one 1-KiB LDS-DMA piece: lane l's 16 bytes at (voff + soff) land at lds_dst + 16*l (lds_dst wave-uniform: it goes to M0)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, unsigned char* lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, (int)voff, (int)soff, 0, 0);
-#endif
-}
-
 // ---------------------------------------------------------------------------------------------
 // Short-K 1x1 with many pixels and many outputs (dense_e2: M = 34 656, N = 2752, K = 96 .. 336): persistent PANEL GEMM.
 // The tiled kernel above pays a workgroup's fixed costs (launch, address set-up, first-load latency, drain) 7859 times per layer for
@@ -307,13 +275,13 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
   const long items = (long)npan * ntn;
   const int it0 = (int)((long)blockIdx.x * items / gridDim.x), it1 = (int)((long)(blockIdx.x + 1) * items / gridDim.x);
   if (it0 == it1) return;
-  const __amdgpu_buffer_rsrc_t srdO = srd(p.out, p.o_bytes);
-  const __amdgpu_buffer_rsrc_t srdX = srd(p.X, p.x_bytes);
-  const __amdgpu_buffer_rsrc_t srdE = srd(wave == 0 ? p.oscale : p.oshift, (unsigned)(p.N * 4));
+  const __amdgpu_buffer_rsrc_t srdO = make_srd(p.out, p.o_bytes);
+  const __amdgpu_buffer_rsrc_t srdX = make_srd(p.X, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t srdE = make_srd(wave == 0 ? p.oscale : p.oshift, (unsigned)(p.N * 4));
   const bool bnrelu = p.scale != nullptr, oact = p.oscale != nullptr;
 
   // DMA pieces of this wave: piece q = wave + 8*j of the item's NKS*12 (step = q / 12, 8 rows x 128 B each); the last column tile is ragged
-  const __amdgpu_buffer_rsrc_t srdW = srd(p.W, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t srdW = make_srd(p.W, p.w_bytes);
   unsigned voff[PW], lastmask = 0;                                    // bit j: piece j's row exists in the (ragged) last column tile
 #pragma unroll
   for (int j = 0; j < PW; ++j) {
@@ -330,14 +298,13 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
     const bool last = t == ntn - 1;
 #pragma unroll
     for (int j = 0; j < PW; ++j)
-      if (wave + 8 * j < NPIECE) dma16(srdW, (!last || ((lastmask >> j) & 1)) ? voff[j] : OOB, so, dst + (wave + 8 * j) * 1024);
-    if (wave < 2) dma16(srdE, (oact && !(last && (ntn - 1) * BN + (int)(lane * 4) >= p.N)) ? evoff : OOB, (unsigned)(t * BN * 4), smem + 2 * BUF + (item & 3) * PANEL_EPI + wave * 1024);
+      if (wave + 8 * j < NPIECE) lds_dma16(srdW, (!last || ((lastmask >> j) & 1)) ? voff[j] : OOB, so, dst + (wave + 8 * j) * 1024);
+    if (wave < 2) lds_dma16(srdE, (oact && !(last && (ntn - 1) * BN + (int)(lane * 4) >= p.N)) ? evoff : OOB, (unsigned)(t * BN * 4), smem + 2 * BUF + (item & 3) * PANEL_EPI + wave * 1024);
   };
 
   bf16x8 xr[2][NKK];
   f32x4 acc[2][6];
   const unsigned sw = (unsigned)((l16 >> 1) & 7);
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   auto mma = [&](int item) {                                            // acc = the item's 32 x 96 products
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -368,8 +335,6 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
   // negative int16), the column offset in the store's scalar offset, one out-of-range select per row instead of one per store.
   // (Tried without effect on the 88 us of the K = 240 layer: the second wave of each SIMD running its epilogue one item late; a per-wave
   // LDS transpose to 16-byte stores of 192 contiguous bytes per row; a pre-tiled weight image with 1-KiB contiguous DMA pieces.)
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef short i16x2 __attribute__((ext_vector_type(2)));
   auto epilogue = [&](int m0, int n0, int slot) {
     const float* const ep = reinterpret_cast<const float*>(smem + 2 * BUF + (slot & 3) * PANEL_EPI);
     const bool ragged = n0 + BN > p.N;                                  // (uniform) the last column tile: per-lane column checks
@@ -391,8 +356,8 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
         if (oact) { a01 = __builtin_elementwise_fma(a01, os01, oh01); a23 = __builtin_elementwise_fma(a23, os23, oh23); }
         unsigned p01 = pack2(a01[0], a01[1]), p23 = pack2(a23[0], a23[1]);
         if (oact) {
-          p01 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(i16x2, p01), i16x2{0, 0}));
-          p23 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(i16x2, p23), i16x2{0, 0}));
+          p01 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p01), s16x2{0, 0}));
+          p23 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p23), s16x2{0, 0}));
         }
         const u32x2 pk = {p01, p23};
         unsigned off = rowoff[i];
@@ -420,7 +385,7 @@ __global__ __launch_bounds__(512, 2) void gemm_panel_bf16_kernel(GemmBf16Args p)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int m = m0 + i * 16 + l16, k0 = kk * 32 + g * 8;
-          const uint4 v = bld(srdX, (k0 < p.K && m < p.M) ? (unsigned)m * (unsigned)(p.ldx * 2) + (unsigned)(k0 * 2) : OOB);   // K is a multiple of 8; past K: zeros
+          const uint4 v = bld_u4(srdX, (k0 < p.K && m < p.M) ? (unsigned)m * (unsigned)(p.ldx * 2) + (unsigned)(k0 * 2) : OOB);   // K is a multiple of 8; past K: zeros
           xr[i][kk] = __builtin_bit_cast(bf16x8, v);
         }
       __builtin_amdgcn_sched_barrier(0);
@@ -475,8 +440,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(Conv3Bf16Args p) {
   const int l16 = lane & 15, g = lane >> 4;
   const int wrow = wave * MT * 16;
   const int m0 = blockIdx.x * BM;
-  const __amdgpu_buffer_rsrc_t srdY = srd(p.Y, p.y_bytes), srdW = srd(p.Wt, p.w_bytes);
-  const __amdgpu_buffer_rsrc_t srdS = srd(p.scale, p.p_bytes), srdT = srd(p.shift, p.p_bytes);
+  const __amdgpu_buffer_rsrc_t srdY = make_srd(p.Y, p.y_bytes), srdW = make_srd(p.Wt, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t srdS = make_srd(p.scale, p.p_bytes), srdT = make_srd(p.shift, p.p_bytes);
 
   auto prow_of = [&](int m, int& x) {                                 // padded row (global over the batch) and column of pixel m
     const int hw = H * W, b = m / hw, rem = m - b * hw, y = rem / W;
@@ -534,13 +499,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(Conv3Bf16Args p) {
     // activation row continues with the next pixel there) and their affine to 0, so relu(0 * 0 + 0) * 0 contributes nothing.
     const bool kok = cs * CS + ch * 8 < p.C;
 #pragma unroll
-    for (int i = 0; i < HL; ++i) rh[i] = bld(srdY, (kok && hoff[i] != OOB) ? hoff[i] + cb : OOB);
+    for (int i = 0; i < HL; ++i) rh[i] = bld_u4(srdY, (kok && hoff[i] != OOB) ? hoff[i] + cb : OOB);
 #pragma unroll
-    for (int i = 0; i < WLN; ++i) rw[i] = bld(srdW, (kok && woff[i] != OOB) ? woff[i] + cb : OOB);
+    for (int i = 0; i < WLN; ++i) rw[i] = bld_u4(srdW, (kok && woff[i] != OOB) ? woff[i] + cb : OOB);
     if (bn) {
       const unsigned po = kok ? (unsigned)((cs * CS + ch * 8) * 4) : OOB;
-      sa = bldf(srdS, po); sb = bldf(srdS, po == OOB ? OOB : po + 16);
-      ta = bldf(srdT, po); tb = bldf(srdT, po == OOB ? OOB : po + 16);
+      sa = bld_f4(srdS, po); sb = bld_f4(srdS, po == OOB ? OOB : po + 16);
+      ta = bld_f4(srdT, po); tb = bld_f4(srdT, po == OOB ? OOB : po + 16);
     }
   };
   auto store_slab = [&]() {
@@ -688,7 +653,7 @@ __global__ __launch_bounds__(NC * 128, 2) void conv3x3_act_bf16_kernel(Conv3ActA
 
   if (loader) {
     const int lw = wave - NC;
-    const __amdgpu_buffer_rsrc_t srdY = srd(p.Y, p.y_bytes), srdW = srd(p.Wimg, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t srdY = make_srd(p.Y, p.y_bytes), srdW = make_srd(p.Wimg, p.w_bytes);
     // image pieces of this wave: piece q = lw + i*NC covers slots 16q .. 16q+15; lane -> (slot, LDS chunk); the SOURCE chunk is swizzled
     unsigned voff[HP];
 #pragma unroll
@@ -705,10 +670,10 @@ __global__ __launch_bounds__(NC * 128, 2) void conv3x3_act_bf16_kernel(Conv3ActA
       const unsigned so = (unsigned)cs * 64u, wso = (unsigned)cs * (unsigned)ACT_W_BYTES;
 #pragma unroll
       for (int i = 0; i < HP; ++i)
-        if (lw + i * NC < npieces) dma16(srdY, voff[i], so, ib + (lw + i * NC) * 1024);
+        if (lw + i * NC < npieces) lds_dma16(srdY, voff[i], so, ib + (lw + i * NC) * 1024);
 #pragma unroll
       for (int q = 0; q < WP; ++q)
-        if (lw + q * NC < WPIECES) dma16(srdW, wvoff + (unsigned)((lw + q * NC) * 1024), wso, wb + (lw + q * NC) * 1024);
+        if (lw + q * NC < WPIECES) lds_dma16(srdW, wvoff + (unsigned)((lw + q * NC) * 1024), wso, wb + (lw + q * NC) * 1024);
     };
     issue(0, cs0);
     for (int cs = cs0; cs < cs1; ++cs) {
@@ -812,7 +777,7 @@ __global__ __launch_bounds__(NC * 128, 2) void conv3x3_act_bf16_kernel(Conv3ActA
   // L2 each time: measured 65 us of a 170 us launch): the partial sums are written and read with agent-scope (sc1) accesses, which
   // go through to the memory side; ordering = this wave's stores acknowledged (vmcnt(0)) -> workgroup barrier -> ticket (device-scope
   // atomic at the memory side) -> the last workgroup's sc1 loads.
-  const __amdgpu_buffer_rsrc_t srdP = srd(p.partial + (size_t)tile * split * (size_t)(BM * 48), (unsigned)(split * BM * 48 * 4));
+  const __amdgpu_buffer_rsrc_t srdP = make_srd(p.partial + (size_t)tile * split * (size_t)(BM * 48), (unsigned)(split * BM * 48 * 4));
   if (store) {
     const unsigned mine = (unsigned)blockIdx.y * (unsigned)(BM * 48 * 4);
 #pragma unroll

@@ -293,12 +293,6 @@ int launch_zero_rows(float* p, long rows, long row_floats, long ld, hipStream_t 
 // co-resident wave (<= 64 VGPRs fit beside the two) gets the issue slots the older waves leave over.  Hence: SRD buffer accesses with
 // the row advance in an SGPR offset (no vector address arithmetic at all), packed v_pk_fma_f32 (4 instead of 8 FMAs per float4),
 // x (1/count) instead of eight f64 divisions per thread, and half as many, longer workgroups.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
-typedef float f32x4e __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2e __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2e __attribute__((ext_vector_type(2)));
-
 // BF (mixed-precision arithmetic mode, RDM_NET_OPT_GEMM_BF16): dz and dst are bf16 rows (ldz / ldd in ELEMENTS of that type) - the consumers of dst
 // (the 1x1 dgrad / wgrad on bf16 operands) round it to bf16 anyway, so storing it as bf16 loses nothing and halves two of the three streams
 // SP (split rows, xsplit_dev.h): dst is written as [hi x4 | lo x4] bf16 groups at the addresses of the float32 values - the two consumers of dY (the
@@ -333,9 +327,9 @@ __global__ __launch_bounds__(256, 8) void k_bn_bwd_apply(float* dst, int ldd, co
     if (dgamma) { dgamma[c] = dg[0]; dgamma[c + 1] = dg[1]; dgamma[c + 2] = dg[2]; dgamma[c + 3] = dg[3]; }
     if (dbeta) { dbeta[c] = db[0]; dbeta[c + 1] = db[1]; dbeta[c + 2] = db[2]; dbeta[c + 3] = db[3]; }
   }
-  const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)dst_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dz), 0, (int)dz_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rd = make_srd(dst, dst_bytes);
+  const __amdgpu_buffer_rsrc_t rz = make_srd(dz, dz_bytes);
+  const __amdgpu_buffer_rsrc_t rx = make_srd(x, x_bytes);
   const int m0 = blockIdx.y * rows_per_block, m1 = min(M, m0 + rows_per_block);
   // per-lane byte offsets of row (m0 + rsub); rows advance by 4 through the scalar offset.  All extents < 4 GiB (launcher).
   constexpr unsigned EZ = BF ? 2u : 4u;                                // bytes per element of dz / dst
@@ -343,25 +337,25 @@ __global__ __launch_bounds__(256, 8) void k_bn_bwd_apply(float* dst, int ldd, co
                  vd = ((unsigned)rsub * (unsigned)ldd + (unsigned)c) * EZ;
   unsigned sz = (unsigned)m0 * (unsigned)ldz * EZ, sx = (unsigned)m0 * (unsigned)ldx * 4u, sd = (unsigned)m0 * (unsigned)ldd * EZ;
   const unsigned dzs = (unsigned)ldz * 4u * EZ, dxs = (unsigned)ldx * 16u, dds = (unsigned)ldd * 4u * EZ;      // 4 rows
-  auto ldz4 = [&](int voff, unsigned soff) -> u32x4e {                // 4 values of dz as float bits
+  auto ldz4 = [&](int voff, unsigned soff) -> u32x4 {                // 4 values of dz as float bits
     if constexpr (BF) {
-      const u32x2e h = __builtin_amdgcn_raw_buffer_load_b64(rz, voff, (int)soff, 0);
-      return u32x4e{h.x << 16, h.x & 0xFFFF0000u, h.y << 16, h.y & 0xFFFF0000u};
+      const u32x2 h = __builtin_amdgcn_raw_buffer_load_b64(rz, voff, (int)soff, 0);
+      return u32x4{h.x << 16, h.x & 0xFFFF0000u, h.y << 16, h.y & 0xFFFF0000u};
     } else {
       return __builtin_amdgcn_raw_buffer_load_b128(rz, voff, (int)soff, 0);
     }
   };
-  auto st4 = [&](u32x4e r, int voff, unsigned soff) {
+  auto st4 = [&](u32x4 r, int voff, unsigned soff) {
     if constexpr (BF) {
-      const bf16x2e lo = {(__bf16)__uint_as_float(r.x), (__bf16)__uint_as_float(r.y)}, hi = {(__bf16)__uint_as_float(r.z), (__bf16)__uint_as_float(r.w)};
-      __builtin_amdgcn_raw_buffer_store_b64(u32x2e{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)}, rd, voff, (int)soff, 0);
+      const bf16x2 lo = {(__bf16)__uint_as_float(r.x), (__bf16)__uint_as_float(r.y)}, hi = {(__bf16)__uint_as_float(r.z), (__bf16)__uint_as_float(r.w)};
+      __builtin_amdgcn_raw_buffer_store_b64(u32x2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)}, rd, voff, (int)soff, 0);
     } else if constexpr (SP) {
       buffer_store_b128_soffset(split_row4(__uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), __uint_as_float(r.w)), rd, voff, (int)soff);
     } else {
       buffer_store_b128_soffset(r, rd, voff, (int)soff);            // (SGPR soffset: protected form, see rdm_common.h)
     }
   };
-  auto one = [&](u32x4e z, u32x4e xv, u32x4e o) {
+  auto one = [&](u32x4 z, u32x4 xv, u32x4 o) {
     f32x2 z0 = {__uint_as_float(z.x), __uint_as_float(z.y)}, z1 = {__uint_as_float(z.z), __uint_as_float(z.w)};
     f32x2 x0 = {__uint_as_float(xv.x), __uint_as_float(xv.y)}, x1 = {__uint_as_float(xv.z), __uint_as_float(xv.w)};
     f32x2 r0 = __builtin_elementwise_fma(a[0], z0, __builtin_elementwise_fma(b[0], x0, cc[0]));
@@ -370,12 +364,12 @@ __global__ __launch_bounds__(256, 8) void k_bn_bwd_apply(float* dst, int ldd, co
       r0 += (f32x2){__uint_as_float(o.x), __uint_as_float(o.y)};
       r1 += (f32x2){__uint_as_float(o.z), __uint_as_float(o.w)};
     }
-    u32x4e r = {__float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r1.x), __float_as_uint(r1.y)};
+    u32x4 r = {__float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r1.x), __float_as_uint(r1.y)};
     return r;
   };
   int m = m0;
   for (; m + 16 <= m1; m += 16) {                                     // 4 row groups in flight; every lane's row is < m1 here
-    u32x4e z[4], xv[4], o[4];
+    u32x4 z[4], xv[4], o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       z[k] = ldz4((int)vz, sz + k * dzs);
@@ -388,9 +382,9 @@ __global__ __launch_bounds__(256, 8) void k_bn_bwd_apply(float* dst, int ldd, co
   }
   for (; m < m1; m += 4) {                                            // tail: rows >= m1 belong to the next workgroup (or do not exist)
     const bool ok = m + rsub < m1;
-    const u32x4e z = ldz4(ok ? (int)vz : -1, sz);
-    const u32x4e xv = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? (int)vx : -1, (int)sx, 0);
-    u32x4e o = {0u, 0u, 0u, 0u};
+    const u32x4 z = ldz4(ok ? (int)vz : -1, sz);
+    const u32x4 xv = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? (int)vx : -1, (int)sx, 0);
+    u32x4 o = {0u, 0u, 0u, 0u};
     if (ACC) o = __builtin_amdgcn_raw_buffer_load_b128(rd, ok ? (int)vd : -1, (int)sd, 0);
     st4(one(z, xv, o), ok ? (int)vd : -1, sd);
     sz += dzs; sx += dxs; sd += dds;
@@ -429,15 +423,15 @@ __global__ __launch_bounds__(256) void k_split_rows(const float* __restrict__ sr
   // a thread keeps its channel quad (and its BatchNorm coefficients) and walks rows: no division per element
   const int c = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
   if (c >= C4 * 4) return;
-  f32x4e sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-  if (scale) { sc = *reinterpret_cast<const f32x4e*>(scale + c); sh = *reinterpret_cast<const f32x4e*>(shift + c); }
+  f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+  if (scale) { sc = *reinterpret_cast<const f32x4*>(scale + c); sh = *reinterpret_cast<const f32x4*>(shift + c); }
   for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    f32x4e v = *reinterpret_cast<const f32x4e*>(src + (long)m * lds_ + c);
+    f32x4 v = *reinterpret_cast<const f32x4*>(src + (long)m * lds_ + c);
     if (scale) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = fmaxf(fmaf(v[e], sc[e], sh[e]), 0.f);
     }
-    *reinterpret_cast<xs_u32x4*>(dst + (long)m * ldd + c) = split_row4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<u32x4*>(dst + (long)m * ldd + c) = split_row4(v[0], v[1], v[2], v[3]);
   }
 }
 

@@ -29,7 +29,6 @@
 
 namespace rdm {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int BK = 16;
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -64,32 +63,7 @@ __device__ __forceinline__ void mma_slab(const float* __restrict__ As, const flo
       for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks][i], b[ks][j], acc[i][j], 0, 0, 0);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Global operands are read through buffer descriptors (SRD): 32-bit byte offsets instead of 64-bit
-// pointer arithmetic, and the hardware range check returns 0 for an out-of-range offset - so zero
-// padding, ragged tile edges and the K tail cost one v_cndmask (offset := ~0u) instead of a
-// divergent branch per load.  Every operand extent is < 4 GiB (checked by the launchers).
-// ---------------------------------------------------------------------------------------------
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0xFFFFFFFFu;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 bld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
-// ---------------------------------------------------------------------------------------------
-// XCD-aware block order.  Workgroups are dealt round-robin over the 8 XCDs in dispatch order
-// (x fastest), and each XCD has its own 4 MB L2: with the plain order the gx column tiles that
-// share one A row-tile land on 8 different L2s and the tile is pulled over the fabric up to 8 times
-// (the 1x1 dgrad of dense_e2 read 3.5x its operand bytes).  Remapped, XCD x works through the
-// contiguous range [x*total/8, (x+1)*total/8) of the logical (x fastest) order, so blocks that are
-// adjacent in time on one XCD are adjacent column tiles of the same row-tile.  A bijection for any
-// grid size; placement only affects speed, never results.  A/B on dense_e2: 1x1 dgrad 116.6 vs 109.7 TFLOP/s.
-// ---------------------------------------------------------------------------------------------
+// XCD-aware block order (dev_prims.h: xcd_logical), over a 3-D grid.
 // flat: 0 = XCD-aware, 1 = hardware order, G >= 2 = XCD-aware AND row-grouped: inside an XCD's range the tiles are walked in groups
 // of G row-tiles, column by column (G blocks in a row share one WEIGHT tile, the group's G activation tiles stay in L2 across all
 // columns).  For the 3x3 dgrad of dense_e2 (57 column tiles x 83 KB of weights = 4.7 MB, more than one L2 holds) the plain order
@@ -99,8 +73,7 @@ __device__ __forceinline__ void xcd_block_order(int flat, int& bx, int& by, int&
   if (flat == 1) return;
   const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
   const unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  const unsigned x = L & 7u, seq = L >> 3, q = total >> 3, r = total & 7u;
-  const unsigned Lp = x * q + (x < r ? x : r) + seq;
+  const unsigned Lp = xcd_logical(L, total);
   if (flat >= 2 && gridDim.z == 1) {
     const unsigned G = (unsigned)flat, gsz = G * gx, grp = Lp / gsz, rem = Lp - grp * gsz;
     const unsigned rows = min(G, gy - grp * G);                       // the last group may be short
@@ -273,12 +246,12 @@ __global__ __launch_bounds__(256, 4) void conv_fwd_kernel(FwdArgs p) {
         ok = ok & ((unsigned)iy < (unsigned)G.H) & ((unsigned)ix < (unsigned)G.W);
       }
       rok[i] = ok;
-      ra[i] = bld4(srdA, ok ? a_voff[i] + a_uni : OOB);
+      ra[i] = bld_f4(srdA, ok ? a_voff[i] + a_uni : OOB);
     }
     if (RAWBN) { rsc = ld4(Sbn + c0 + kq_a * 4); rsh = ld4(Sbn + RAWBN_MAX_C + c0 + kq_a * 4); }
     else if (bnrelu) { rsc = ld4(p.a_scale + c0 + kq_a * 4); rsh = ld4(p.a_shift + c0 + kq_a * 4); }
 #pragma unroll
-    for (int i = 0; i < BL; ++i) rb[i] = bld4(srdW, b_voff[i] == OOB ? OOB : b_voff[i] + b_uni);
+    for (int i = 0; i < BL; ++i) rb[i] = bld_f4(srdW, b_voff[i] == OOB ? OOB : b_voff[i] + b_uni);
   };
   auto store_slab = [&](int buf) {
 #pragma unroll
@@ -346,12 +319,6 @@ __global__ __launch_bounds__(256, 4) void conv_fwd_kernel(FwdArgs p) {
 // row.  Lane (row, kq) takes channels 4kq .. 4kq+3 of the slab and feeds element e to MFMA step e - a permutation of k shared by
 // both operands.  The consumer BN-ReLU is applied to the A fragments (8 VALU per 16-row tile and slab next to 16 MFMAs).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float* lds_dst) {
-#if defined(__HIP_DEVICE_COMPILE__)      // (the host pass cannot type-check the gfx950 builtin and would silently drop the kernel's stub)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, (int)voff, (int)soff, 0, 0);
-#endif
-}
-
 template <int EPI, bool BNRELU, int MT = 8>      // MT = 8: 256 x 128 macro tile; MT = 6: 192 x 128 (chosen where it fills the workgroup rounds better)
 __global__ __launch_bounds__(256, 2) void conv1x1_dma256_kernel(FwdArgs p) {
   constexpr int NT = 4, BM = MT * 32, BN = 128, NBUF = 3, NA = BM / 16 / 4, NB = BN / 16 / 4;      // 1-KiB pieces (16 rows x 64 B) per wave and slab: 4 (3) + 2
@@ -518,7 +485,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_halo_kernel(FwdArgs p) {
   auto load_halo = [&](int cs) {
     const unsigned uni = (unsigned)(cs * BK * 4);
 #pragma unroll
-    for (int i = 0; i < HL; ++i) rh[i] = bld4(srdA, h_ok[i] ? h_voff[i] + uni : OOB);
+    for (int i = 0; i < HL; ++i) rh[i] = bld_f4(srdA, h_ok[i] ? h_voff[i] + uni : OOB);
     if (RAWBN) { rsc = ld4(Sbn + cs * BK + kq_a * 4); rsh = ld4(Sbn + RAWBN_MAX_C + cs * BK + kq_a * 4); }
     else if (bnrelu) { rsc = ld4(p.a_scale + cs * BK + kq_a * 4); rsh = ld4(p.a_shift + cs * BK + kq_a * 4); }
   };
@@ -542,7 +509,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_halo_kernel(FwdArgs p) {
   float4 rb;
   auto load_b = [&](int cs, int tap) {
     const unsigned uni = (unsigned)tap * (unsigned)(p.wtap * 4) + (DGRAD ? (unsigned)(cs * BK) * (unsigned)(p.ldw * 4) : (unsigned)(cs * BK * 4));
-    rb = bld4(srdW, b_act ? b_voff + uni : OOB);
+    rb = bld_f4(srdW, b_act ? b_voff + uni : OOB);
   };
   auto store_b = [&](int buf) {
     if (tid < BN * 4) {
@@ -679,10 +646,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(WgradArgs p) {
   const int ntaps_g = TAPS ? G.KH * G.KW : 1;
   int tap = 0;
   long item = blockIdx.x;
-  if (!TAPS && !p.xcd_flat) {                       // XCD x works through a contiguous range of items (see xcd_block_order)
-    const unsigned total = gridDim.x, L = blockIdx.x, x = L & 7u, q = total >> 3, r = total & 7u;
-    item = x * q + (x < r ? x : r) + (L >> 3);
-  }
+  if (!TAPS && !p.xcd_flat) item = xcd_logical(blockIdx.x, gridDim.x);      // XCD x works through a contiguous range of items
   if (TAPS) {
     const long L = blockIdx.x, lane8 = L & 7, seq = L >> 3;
     tap = (int)(seq % ntaps_g);
@@ -741,7 +705,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(WgradArgs p) {
 #pragma unroll
     for (int i = 0; i < AL; ++i) {
       const bool okm = a_m[i] < Mpix;
-      ra[i] = bld4(srdG, okm ? a_voff[i] : OOB);
+      ra[i] = bld_f4(srdG, okm ? a_voff[i] : OOB);
       a_m[i] += BK; a_voff[i] += (unsigned)(BK * p.ldg * 4);
     }
 #pragma unroll
@@ -757,7 +721,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(WgradArgs p) {
         while (poy[i] >= G.Ho) { poy[i] -= G.Ho; ++pb_[i]; }
       }
       rok[i] = ok;
-      rb[i] = bld4(srdX, ok ? (unsigned)pix * (unsigned)(p.ldx * 4) + b_col[i] : OOB);
+      rb[i] = bld_f4(srdX, ok ? (unsigned)pix * (unsigned)(p.ldx * 4) + b_col[i] : OOB);
       b_m[i] += BK;
     }
   };

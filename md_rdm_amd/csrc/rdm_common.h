@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../../include/rdm_hip.h"
+#include "dev_prims.h"
 
 namespace rdm {
 
@@ -156,8 +157,7 @@ int launch_nyu_preprocess(const unsigned char* rgb, const float* depth, const vo
 // round 4 as "wrong values in lanes 12-15" of xs_dgrad3x3_kernel's gated output.)  Every >64-bit buffer store with a runtime scalar offset goes
 // through this helper: the store and its two wait states are one asm block, so no schedule can separate them.
 // tools/store_hazard/scan_isa.py audits the compiled ISA of the whole library for the unprotected pattern (tests/test_isa_hazard.py runs it).
-typedef unsigned int rdm_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void buffer_store_b128_soffset(rdm_u32x4 data, __amdgpu_buffer_rsrc_t srd, int voffset, int soffset) {
+__device__ __forceinline__ void buffer_store_b128_soffset(u32x4 data, __amdgpu_buffer_rsrc_t srd, int voffset, int soffset) {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" : : "v"(data), "v"(voffset), "s"(srd), "s"(soffset) : "memory");
 #endif

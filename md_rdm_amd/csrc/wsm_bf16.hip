@@ -29,11 +29,6 @@
 
 namespace rdm {
 
-typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
-typedef float f32x4w __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4w __attribute__((ext_vector_type(4)));
-constexpr unsigned WOOB = 0xFFFFFFFFu;
-
 enum { WSM_PLAIN = 0, WSM_SHUFFLE = 1, WSM_BCAST_ROWS = 2, WSM_BCAST_COLS = 3, WSM_F32 = 4 };
 
 struct WsmSeg {
@@ -52,20 +47,10 @@ struct WsmConvArgs {
   int S;                                        // BCAST: broadcast length
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wsrd(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint4 wbld(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  const u32x4w v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ unsigned short bf1(float a) { return __builtin_bit_cast(unsigned short, (__bf16)a); }
-__device__ __forceinline__ unsigned wpack2(float a, float b) { return (unsigned)bf1(a) | ((unsigned)bf1(b) << 16); }
-
 // 4 consecutive channels of one pixel: one 8-byte store when all four are stored and 8-byte aligned, else 2-byte stores
 __device__ __forceinline__ void st4(unsigned short* p, float v0, float v1, float v2, float v3, int cnt) {
   if (cnt >= 4 && (((uintptr_t)p & 7) == 0)) {
-    *reinterpret_cast<uint2*>(p) = make_uint2(wpack2(v0, v1), wpack2(v2, v3));
+    *reinterpret_cast<uint2*>(p) = make_uint2(pack2_scalar(v0, v1), pack2_scalar(v2, v3));
     return;
   }
   if (cnt > 0) p[0] = bf1(v0);
@@ -91,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void wsm_conv_bf16_kernel(WsmConvArgs p) {
   const int wrow = (wave >> 1) * MT * 16, wcol = (wave & 1) * NT * 16;
   const int n0 = blockIdx.x * BN, m0 = blockIdx.y * BM;
   const int HW = p.H * p.W, M = p.B * HW;
-  const __amdgpu_buffer_rsrc_t srdX = wsrd(p.X, p.x_bytes), srdW = wsrd(p.Wt, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t srdX = make_srd(p.X, p.x_bytes), srdW = make_srd(p.Wt, p.w_bytes);
 
   const int ch = tid % CH, r0 = tid / CH;
   long xbase[XL];
@@ -111,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void wsm_conv_bf16_kernel(WsmConvArgs p) {
 #pragma unroll
   for (int i = 0; i < WL; ++i) {
     const int n = n0 + r0 + RP * i;
-    woff[i] = n < p.N ? (unsigned)n * (unsigned)(p.K * 2) + (unsigned)(ch * 16) : WOOB;
+    woff[i] = n < p.N ? (unsigned)n * (unsigned)(p.K * 2) + (unsigned)(ch * 16) : OOB;
   }
   struct Stage { uint4 rx[XL]; uint4 rw[WL]; };
   Stage S[2];
@@ -126,11 +111,11 @@ __global__ __launch_bounds__(256, 2) void wsm_conv_bf16_kernel(WsmConvArgs p) {
     for (int i = 0; i < XL; ++i) {
       const int y = xy[i] + dy - p.ph, x = xx[i] + dx - p.pw;
       const bool ok = kok && y >= 0 && y < p.H && x >= 0 && x < p.W;
-      St.rx[i] = wbld(srdX, ok ? (unsigned)((xbase[i] + koff) * 2) : WOOB);
+      St.rx[i] = bld_u4(srdX, ok ? (unsigned)((xbase[i] + koff) * 2) : OOB);
     }
     const unsigned kb = (unsigned)(kt * BK * 2);
 #pragma unroll
-    for (int i = 0; i < WL; ++i) St.rw[i] = wbld(srdW, (kok && woff[i] != WOOB) ? woff[i] + kb : WOOB);
+    for (int i = 0; i < WL; ++i) St.rw[i] = bld_u4(srdW, (kok && woff[i] != OOB) ? woff[i] + kb : OOB);
   };
   auto store_step = [&](int buf, const Stage& St) {
     unsigned short* Xs = Xs0 + buf * BM * BK;
@@ -147,11 +132,11 @@ __global__ __launch_bounds__(256, 2) void wsm_conv_bf16_kernel(WsmConvArgs p) {
     }
   };
 
-  f32x4w acc[MT][NT];
+  f32x4 acc[MT][NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4w{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nk = (p.K + BK - 1) / BK;
   const int sw = swz(l16);
   auto mma_step = [&](int buf) {
@@ -160,11 +145,11 @@ __global__ __launch_bounds__(256, 2) void wsm_conv_bf16_kernel(WsmConvArgs p) {
 #pragma unroll
     for (int ks = 0; ks < BK / 32; ++ks) {
       const int co = ((ks * 4 + g) ^ sw) << 3;
-      bf16x8w wf[NT], xf[MT];
+      bf16x8 wf[NT], xf[MT];
 #pragma unroll
-      for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const bf16x8w*>(Ws + (wcol + j * 16 + l16) * BK + co);
+      for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const bf16x8*>(Ws + (wcol + j * 16 + l16) * BK + co);
 #pragma unroll
-      for (int i = 0; i < MT; ++i) xf[i] = *reinterpret_cast<const bf16x8w*>(Xs + (wrow + i * 16 + l16) * BK + co);
+      for (int i = 0; i < MT; ++i) xf[i] = *reinterpret_cast<const bf16x8*>(Xs + (wrow + i * 16 + l16) * BK + co);
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll

@@ -31,21 +31,7 @@
 
 namespace rdm {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
-
-constexpr unsigned XOOB = 0xFFFFFFFFu;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xsrd(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 // one MFMA operand fragment (8 consecutive k of one row / column) from a [pixel][channel] image: two transposed 8-byte reads
 __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base0, const unsigned char* base1, int imm) {
@@ -106,7 +92,7 @@ __device__ __forceinline__ void xs_wgrad1x1_body(const XsWgradArgs& p, unsigned 
   const int l16 = lane & 15, g = lane >> 4;
   const int grp = tid >> 4, kq = l16 >> 2, jq = l16 & 3;
   const bool bnrelu = p.x_scale != nullptr;
-  const __amdgpu_buffer_rsrc_t srdG = xsrd(p.G, p.g_bytes), srdX = xsrd(p.X, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t srdG = make_srd(p.G, p.g_bytes), srdX = make_srd(p.X, p.x_bytes);
 
   if (bnrelu) {
     for (int i = tid; i < BN; i += 512) {
@@ -150,16 +136,16 @@ __device__ __forceinline__ void xs_wgrad1x1_body(const XsWgradArgs& p, unsigned 
     for (int it = 0; it < 4; ++it) {
       const bool ok = m0 + a_row[it] < p.M;
       if (NP == 1 && p.g_bf16) {
-        const u32x2 h = __builtin_amdgcn_raw_buffer_load_b64(srdG, (int)(ok ? a_voff[it] + sog : XOOB), 0, 0);
+        const u32x2 h = __builtin_amdgcn_raw_buffer_load_b64(srdG, (int)(ok ? a_voff[it] + sog : OOB), 0, 0);
         ra[it] = f32x4{__uint_as_float(h[0]), __uint_as_float(h[1]), 0.f, 0.f};
       } else {
-        ra[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdG, (int)(ok ? a_voff[it] + sog : XOOB), 0, 0));
+        ra[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdG, (int)(ok ? a_voff[it] + sog : OOB), 0, 0));
       }
     }
 #pragma unroll
     for (int it = 0; it < BL; ++it) {
       const bool ok = m0 + b_row[it] < p.M;
-      rb[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)(ok ? b_voff[it] + sox : XOOB), 0, 0));
+      rb[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)(ok ? b_voff[it] + sox : OOB), 0, 0));
       bhi[it] = ok ? __builtin_inff() : 0.f;
     }
   };
@@ -278,7 +264,8 @@ template <int NP>
 __global__ __launch_bounds__(512, 1) void xs_wgrad1x1_kernel(XsWgradArgs p) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * XS_STAGE + 2 * XS_NTMAX * 16 * 4];
   // work item = (column tile, row tile, K split), column tile fastest; XCD x works through a contiguous range of items so that the
-  // column tiles sharing one gradient tile meet in one L2 (placement affects speed only)
+  // column tiles sharing one gradient tile meet in one L2 (placement affects speed only).  This is dev_prims.h xcd_logical with the sequence number
+  // added last; the three 1-D sites of this file keep that order because the helper's changes the schedule of their prologues
   const unsigned total = gridDim.x, L = blockIdx.x, x = L & 7u, q = total >> 3, r = total & 7u;
   const long item = x * q + (x < r ? x : r) + (L >> 3);
   const int ntiles = (p.N + XS_BM - 1) / XS_BM;
@@ -377,7 +364,7 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
   const int it0 = (int)((long)blockIdx.x * T / gridDim.x), it1 = (int)((long)(blockIdx.x + 1) * T / gridDim.x);
   unsigned char* const Ahi = xs_smem;
   unsigned char* const Alo = xs_smem + p.plane_bytes;
-  const __amdgpu_buffer_rsrc_t srdG = xsrd(p.G, p.g_bytes), srdW = xsrd(p.Wf, p.w_bytes), srdX = xsrd(p.X, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t srdG = make_srd(p.G, p.g_bytes), srdW = make_srd(p.Wf, p.w_bytes), srdX = make_srd(p.X, p.x_bytes);
 
   // k-step j -> the lane's chunk: offset of (tap shift, 8-channel group), biased by +32768, two per register
   unsigned dpk[XD_KSTEPS / 2];
@@ -406,7 +393,7 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
           const int idx = b0 + u * 256 + ts, slot = idx / 12, quad = idx - slot * 12;
           const int pix = pbase + slot;
           const bool ok = idx < total4 && pix >= 0 && pix < p.M;
-          v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdG, (int)(ok ? (unsigned)pix * (unsigned)(p.ldg * 4) + (unsigned)(quad * 16) : XOOB), 0, 0));
+          v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdG, (int)(ok ? (unsigned)pix * (unsigned)(p.ldg * 4) + (unsigned)(quad * 16) : OOB), 0, 0));
         }
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
@@ -480,7 +467,7 @@ __global__ __launch_bounds__(256, 2) void xs_dgrad3x3_kernel(XsDgrad3Args p) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int i = c * XD_EC + u;
-          xv[c % (XD_EA + 1)][u][t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)(((t == 0 || t1ok) && ml + i * 16 < p.M) ? vx0 + 64u * t : XOOB), i * 16 * p.ldx * 4, 0));
+          xv[c % (XD_EA + 1)][u][t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)(((t == 0 || t1ok) && ml + i * 16 < p.M) ? vx0 + 64u * t : OOB), i * 16 * p.ldx * 4, 0));
         }
     };
     load_w(0, wf[0]);
@@ -655,7 +642,7 @@ __global__ __launch_bounds__(512, 2) void xs_dgrad1x1_kernel(XsDgrad1Args p) {
   // this wave: 16-channel tiles [tw0, tw0 + ntw) of the column tile, 16-pixel tiles [pw0, pw0 + npw) of the pixel tile
   const int ntw_max = (nct + 1) >> 1, tw0 = wc * ntw_max, ntw = min(ntw_max, nct - tw0);
   const int npw_max = (p.PT + 3) >> 2, pw0 = wp * npw_max, npw = max(0, min(npw_max, p.PT - pw0));
-  const __amdgpu_buffer_rsrc_t srdG = xsrd(p.G, p.g_bytes), srdW = xsrd(p.Wp, p.w_bytes), srdX = xsrd(p.X, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t srdG = make_srd(p.G, p.g_bytes), srdW = make_srd(p.Wp, p.w_bytes), srdX = make_srd(p.X, p.x_bytes);
 
   // ---- staging maps.  Gradient: float4 (row = idx >> 3, 4 k at 4 (idx & 7)) -> 8 B of each plane; weights: 16-byte pieces, verbatim ----
   unsigned g_voff[X1_MTW]; unsigned g_lds[X1_MTW]; int g_k[X1_MTW];
@@ -675,16 +662,16 @@ __global__ __launch_bounds__(512, 2) void xs_dgrad1x1_kernel(XsDgrad1Args p) {
 #pragma unroll
     for (int u = 0; u < X1_MTW; ++u) {
       if (NP == 1 && p.g_bf16) {                                // 4 bf16 = 8 bytes, kept in the first two registers of the set
-        const u32x2 h = __builtin_amdgcn_raw_buffer_load_b64(srdG, (int)((32 * j + g_k[u] < p.K) ? g_voff[u] + (unsigned)(j * 64) : XOOB), 0, 0);
+        const u32x2 h = __builtin_amdgcn_raw_buffer_load_b64(srdG, (int)((32 * j + g_k[u] < p.K) ? g_voff[u] + (unsigned)(j * 64) : OOB), 0, 0);
         rg[set][u] = f32x4{__uint_as_float(h[0]), __uint_as_float(h[1]), 0.f, 0.f};
       } else {
-        rg[set][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdG, (int)((32 * j + g_k[u] < p.K) ? g_voff[u] + (unsigned)(j * 128) : XOOB), 0, 0));
+        rg[set][u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdG, (int)((32 * j + g_k[u] < p.K) ? g_voff[u] + (unsigned)(j * 128) : OOB), 0, 0));
       }
     }
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
       const int q = tid + 512 * u, pl = q >= BN * 4, r = pl ? q - BN * 4 : q;      // piece r of plane pl: row r >> 2, chunk r & 3 (already swizzled in memory)
-      rw[set][u] = __builtin_amdgcn_raw_buffer_load_b128(srdW, (int)((q < wpieces && j < p.ksteps) ? (unsigned)pl * w_plane + ((unsigned)j * (unsigned)p.C + (unsigned)(ct0 * 16)) * 64u + (unsigned)r * 16u : XOOB), 0, 0);
+      rw[set][u] = __builtin_amdgcn_raw_buffer_load_b128(srdW, (int)((q < wpieces && j < p.ksteps) ? (unsigned)pl * w_plane + ((unsigned)j * (unsigned)p.C + (unsigned)(ct0 * 16)) * 64u + (unsigned)r * 16u : OOB), 0, 0);
     }
   };
   auto store_slab = [&](int set, unsigned char* st) {
@@ -769,7 +756,7 @@ __global__ __launch_bounds__(512, 2) void xs_dgrad1x1_kernel(XsDgrad1Args p) {
     if (MASK) {
 #pragma unroll
       for (int i = 0; i < X1_MTW; ++i)
-        xv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)((cok && i < npw && m0 + (pw0 + i) * 16 + l16 < p.M) ? vx : XOOB), i * 16 * p.ldx * 4, 0));
+        xv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)((cok && i < npw && m0 + (pw0 + i) * 16 + l16 < p.M) ? vx : OOB), i * 16 * p.ldx * 4, 0));
     }
 #pragma unroll
     for (int i = 0; i < X1_MTW; ++i) {
@@ -853,7 +840,7 @@ __global__ __launch_bounds__(256, 2) void xs_wgrad3x3_kernel(XsWgrad3Args p) {
   const int per = (p.nslab + p.split - 1) / p.split;
   const int s_begin = blockIdx.y * per, s_end = min(p.nslab, s_begin + per);
   if (s_begin >= s_end) return;
-  const __amdgpu_buffer_rsrc_t srdG = xsrd(p.G, p.g_bytes), srdY = xsrd(p.Y, p.y_bytes);
+  const __amdgpu_buffer_rsrc_t srdG = make_srd(p.G, p.g_bytes), srdY = make_srd(p.Y, p.y_bytes);
   const bool bnrelu = p.y_scale != nullptr;
 
   // ---- staging maps.  Activations: patch (rg = (grp >> 2) + 4 it, ct = grp & 3): slab row 4 rg + kq, channels c0 + 16 ct + 4 jq .. + 3 ----
@@ -861,7 +848,7 @@ __global__ __launch_bounds__(256, 2) void xs_wgrad3x3_kernel(XsWgrad3Args p) {
   const bool ycok = yc < p.C;
   f32x4 ysc = {1.f, 1.f, 1.f, 1.f}, ysh = {0.f, 0.f, 0.f, 0.f};
   if (bnrelu && ycok) { ysc = *reinterpret_cast<const f32x4*>(p.y_scale + yc); ysh = *reinterpret_cast<const f32x4*>(p.y_shift + yc); }
-  // offset of (padded position u, this thread's channel quad) or XOOB for a border / out-of-range position
+  // offset of (padded position u, this thread's channel quad) or OOB for a border / out-of-range position
   // (u < 2^21: floor((u + 0.5) / d) through one float multiply is exact - the quotient's error stays far below the 0.5 / d margin)
   const float rPP = 1.0f / (float)PP, rWp = 1.0f / (float)Wp;
   // (a per-geometry table position -> pixel index in place of this arithmetic - ~20 of the ~45 vector instructions a staged float4 costs - was built and
@@ -876,7 +863,7 @@ __global__ __launch_bounds__(256, 2) void xs_wgrad3x3_kernel(XsWgrad3Args p) {
   auto pix_off = [&](int u, int ld, int col, bool colok) -> unsigned {
     const int b = (int)(((float)u + 0.5f) * rPP), rem = u - b * PP, yp = (int)(((float)rem + 0.5f) * rWp), xp = rem - yp * Wp;
     const bool ok = u >= 0 && u < U && colok && yp >= 1 && yp <= p.H && xp >= 1 && xp <= p.W;
-    return ok ? (unsigned)((b * p.H + yp - 1) * p.W + xp - 1) * (unsigned)(ld * 4) + (unsigned)(col * 4) : XOOB;
+    return ok ? (unsigned)((b * p.H + yp - 1) * p.W + xp - 1) * (unsigned)(ld * 4) + (unsigned)(col * 4) : OOB;
   };
   auto y_lds = [&](int s, int it) -> unsigned {              // ring position of (slab s, this thread's row of patch it)
     const int row = ((s & 7) << 5) + 4 * ((grp >> 2) + 4 * it) + kq;
@@ -892,7 +879,7 @@ __global__ __launch_bounds__(256, 2) void xs_wgrad3x3_kernel(XsWgrad3Args p) {
     for (int it = 0; it < 2; ++it) {
       const unsigned off = pix_off(s * 32 + 4 * ((grp >> 2) + 4 * it) + kq, p.ldy, yc, ycok);
       ry[set][it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdY, (int)off, 0, 0));
-      yin = (yin & ~(1u << (2 * set + it))) | (off != XOOB ? 1u << (2 * set + it) : 0u);
+      yin = (yin & ~(1u << (2 * set + it))) | (off != OOB ? 1u << (2 * set + it) : 0u);
     }
   };
   auto store_y = [&](int set, int s) {
@@ -918,8 +905,8 @@ __global__ __launch_bounds__(256, 2) void xs_wgrad3x3_kernel(XsWgrad3Args p) {
     for (int it = 0; it < 2; ++it) {
       const int pi = grp + 16 * it, rg = pi / 3, ct = pi - 3 * rg;
       unsigned off;
-      if (NP == 3 && p.g_frame) off = (pi < 24 && s >= 0) ? (unsigned)(s * 32 + 4 * rg + kq) * 192u + (unsigned)((16 * ct + 4 * jq) * 4) : XOOB;      // past the image: out of range -> zeros
-      else off = pi < 24 ? pix_off(s * 32 + 4 * rg + kq, p.ldg, 16 * ct + 4 * jq, 16 * ct + 4 * jq < p.N) : XOOB;
+      if (NP == 3 && p.g_frame) off = (pi < 24 && s >= 0) ? (unsigned)(s * 32 + 4 * rg + kq) * 192u + (unsigned)((16 * ct + 4 * jq) * 4) : OOB;      // past the image: out of range -> zeros
+      else off = pi < 24 ? pix_off(s * 32 + 4 * rg + kq, p.ldg, 16 * ct + 4 * jq, 16 * ct + 4 * jq < p.N) : OOB;
       rgv[set][it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdG, (int)off, 0, 0));
     }
   };
@@ -1069,17 +1056,6 @@ struct XsFwd1Args {
   unsigned x_bytes, w_bytes;
 };
 
-__device__ __forceinline__ void split3x4(const f32x4 v, u32x2& p0, u32x2& p1, u32x2& p2) {
-  const bf16x2 a01 = {(__bf16)v[0], (__bf16)v[1]}, a23 = {(__bf16)v[2], (__bf16)v[3]};
-  const float r0 = v[0] - (float)a01[0], r1 = v[1] - (float)a01[1], r2 = v[2] - (float)a23[0], r3 = v[3] - (float)a23[1];
-  const bf16x2 b01 = {(__bf16)r0, (__bf16)r1}, b23 = {(__bf16)r2, (__bf16)r3};
-  const float q0 = r0 - (float)b01[0], q1 = r1 - (float)b01[1], q2 = r2 - (float)b23[0], q3 = r3 - (float)b23[1];
-  const bf16x2 c01 = {(__bf16)q0, (__bf16)q1}, c23 = {(__bf16)q2, (__bf16)q3};
-  p0 = u32x2{__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, a23)};
-  p1 = u32x2{__builtin_bit_cast(unsigned, b01), __builtin_bit_cast(unsigned, b23)};
-  p2 = u32x2{__builtin_bit_cast(unsigned, c01), __builtin_bit_cast(unsigned, c23)};
-}
-
 __global__ __launch_bounds__(256) void k_xs_pack_w1_fwd(const float* __restrict__ w, int ldw, int N, int K, int ksteps, unsigned char* __restrict__ Wp) {
   // one thread per (k-step, n, 8-k chunk): 8 consecutive weights of row n -> 16 B of each of the three planes at the swizzled chunk
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -1095,8 +1071,8 @@ __global__ __launch_bounds__(256) void k_xs_pack_w1_fwd(const float* __restrict_
     v1[e] = k1 < K ? w[(long)n * ldw + k1] : 0.f;
   }
   u32x2 a0, a1, a2, b0, b1, b2;
-  split3x4(v0, a0, a1, a2);
-  split3x4(v1, b0, b1, b2);
+  split3x4(v0[0], v0[1], v0[2], v0[3], a0, a1, a2);
+  split3x4(v1[0], v1[1], v1[2], v1[3], b0, b1, b2);
   const int chs = ch ^ (((n >> 2) & 1) << 1);
   const long plane = (long)ksteps * N * 64;
   unsigned char* dst = Wp + ((long)j * N + n) * 64 + chs * 16;
@@ -1121,7 +1097,7 @@ __global__ __launch_bounds__(512, MTW == 4 ? 2 : 4) void xs_fwd1x1_kernel(XsFwd1
   const int ct0 = ctile * (2 * XF_NTW), nct = min(2 * XF_NTW, p.N / 16 - ct0), BN = nct * 16;
   const int ntw_max = (nct + 1) >> 1, tw0 = wc * ntw_max, ntw = min(ntw_max, nct - tw0);
   const int npw_max = (p.PT + 3) >> 2, pw0 = wp * npw_max, npw = max(0, min(npw_max, p.PT - pw0));
-  const __amdgpu_buffer_rsrc_t srdX = xsrd(p.X, p.x_bytes), srdW = xsrd(p.Wp, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t srdX = make_srd(p.X, p.x_bytes), srdW = make_srd(p.Wp, p.w_bytes);
   const bool bnrelu = p.x_scale != nullptr;
   unsigned char* const Xi = xf_smem;                          // 3 planes of XF_X_IMG
   unsigned char* const Wi = xf_smem + 3 * XF_X_IMG;           // 3 planes of XF_W_IMG
@@ -1142,7 +1118,7 @@ __global__ __launch_bounds__(512, MTW == 4 ? 2 : 4) void xs_fwd1x1_kernel(XsFwd1
     const bool kok = 32 * j + 4 * f4 < p.K;
 #pragma unroll
     for (int u = 0; u < XF_MTW; ++u)
-      rx[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)((x_ok[u] && kok) ? x_voff[u] + (unsigned)(j * 128) : XOOB), 0, 0));
+      rx[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srdX, (int)((x_ok[u] && kok) ? x_voff[u] + (unsigned)(j * 128) : OOB), 0, 0));
     if (bnrelu) {
       sc = kok ? *reinterpret_cast<const f32x4*>(p.x_scale + 32 * j + 4 * f4) : f32x4{0.f, 0.f, 0.f, 0.f};
       sh = kok ? *reinterpret_cast<const f32x4*>(p.x_shift + 32 * j + 4 * f4) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1150,7 +1126,7 @@ __global__ __launch_bounds__(512, MTW == 4 ? 2 : 4) void xs_fwd1x1_kernel(XsFwd1
 #pragma unroll
     for (int u = 0; u < 5; ++u) {
       const int q = tid + 512 * u, pl = q / wpieces, r = q - pl * wpieces;        // piece r of plane pl
-      rw[u] = __builtin_amdgcn_raw_buffer_load_b128(srdW, (int)(q < 3 * wpieces ? (unsigned)pl * w_plane + ((unsigned)j * (unsigned)p.N + (unsigned)(ct0 * 16)) * 64u + (unsigned)r * 16u : XOOB), 0, 0);
+      rw[u] = __builtin_amdgcn_raw_buffer_load_b128(srdW, (int)(q < 3 * wpieces ? (unsigned)pl * w_plane + ((unsigned)j * (unsigned)p.N + (unsigned)(ct0 * 16)) * 64u + (unsigned)r * 16u : OOB), 0, 0);
     }
   };
   auto store_slab = [&]() {
@@ -1164,7 +1140,7 @@ __global__ __launch_bounds__(512, MTW == 4 ? 2 : 4) void xs_fwd1x1_kernel(XsFwd1
           for (int e = 0; e < 4; ++e) v[e] = fmaxf(fmaf(v[e], sc[e], sh[e]), 0.f);
         }
         u32x2 p0, p1, p2;
-        split3x4(v, p0, p1, p2);
+        split3x4(v[0], v[1], v[2], v[3], p0, p1, p2);
         *reinterpret_cast<u32x2*>(Xi + x_lds[u]) = p0;
         if (NP == 6) {
           *reinterpret_cast<u32x2*>(Xi + XF_X_IMG + x_lds[u]) = p1;
