@@ -255,6 +255,25 @@ int rdm_conv3x3_act_bf16_pack(const float* w_oihw, int32_t channels, void* w_ima
 size_t rdm_conv3x3_act_bf16_workspace_bytes(int32_t channels_padded, int32_t batch, int32_t h, int32_t w);
 int rdm_conv3x3_act_bf16(const void* y_act, int32_t ldy, int32_t channels_padded, const void* w_image, void* out, int32_t ldc, int32_t batch,
                          int32_t h, int32_t w, void* workspace, size_t workspace_bytes, rdm_stream_t stream);
+/* The helper kernels of rdm_net_forward_bf16 / rdm_net_bf16_prepare as operators (the plan enqueues the same kernels).  Every bf16 tensor is
+ * 16-byte aligned; channel counts and pixel / row strides of bf16 tensors are multiples of 8, stride >= channels.
+ *   rdm_stem_patches_bf16      x (B,3,H,W) f32 NCHW -> patches (B*Ho*Wo, 160) bf16 of the 7x7 / stride 2 / pad 3 stem (RDM_Net.py:524), Ho = (H-1)/2+1:
+ *                              column k = c*49 + r*7 + s holds x[b][c][2oy-3+r][2ox-3+s] (0 outside the image), columns 147..159 are zero.
+ *   rdm_maxpool3s2_bf16        nn.MaxPool2d(3, 2, 1) (:525): x (B,H,W, channels) bf16 contiguous (pixel stride = channels) -> y (B*Ho*Wo, ldy) bf16,
+ *                              Ho = (H-1)/2+1; the padding never wins.
+ *   rdm_padavgpool2_bf16       the transition front end (:527,529,531-532): pad bottom / right to even sizes with zeros -> x*scale[c]+shift[c] -> ReLU ->
+ *                              2x2 average, one rounding to bf16.  x (B,H,W, ldx) bf16, scale / shift f32[channels] (16-byte aligned),
+ *                              out (B*Ho*Wo, channels) bf16 contiguous, Ho = (H+1)/2.  The zero pad is a BatchNorm input: it contributes relu(shift).
+ *   rdm_f32_to_bf16_rows       dst[r][c] = bf16(src[r][c]) for c < cols, 0 for cols <= c < cols_pad; src (rows, ld_src) f32, dst (rows, ld_dst) bf16,
+ *                              ld_src >= cols, ld_dst >= cols_pad >= cols, ld_dst a multiple of 8.  Columns from cols_pad on are left alone.
+ *   rdm_pack_conv_weight_bf16  w (out_c, in_c, taps) f32 (PyTorch OIHW, taps = kh*kw) -> w_packed [taps][out_c][ld] bf16, ld >= in_c a multiple of 8;
+ *                              columns in_c .. ld-1 are left alone (the caller zeroes them). */
+int rdm_stem_patches_bf16(const float* x_nchw, void* patches, int32_t batch, int32_t h, int32_t w, rdm_stream_t stream);
+int rdm_maxpool3s2_bf16(const void* x, void* y, int32_t ldy, int32_t batch, int32_t h, int32_t w, int32_t channels, rdm_stream_t stream);
+int rdm_padavgpool2_bf16(const void* x, int32_t ldx, const float* scale, const float* shift, void* out, int32_t batch, int32_t h, int32_t w,
+                         int32_t channels, rdm_stream_t stream);
+int rdm_f32_to_bf16_rows(const float* src, int32_t ld_src, void* dst, int32_t ld_dst, int64_t rows, int32_t cols, int32_t cols_pad, rdm_stream_t stream);
+int rdm_pack_conv_weight_bf16(const float* w_oihw, void* w_packed, int32_t out_c, int32_t in_c, int32_t ld, int32_t taps, rdm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * BatchNorm / pooling pieces of the conv stack as operators (the plan below enqueues the same kernels).

@@ -64,6 +64,11 @@ _SIGNATURES = {
     "rdm_conv3x3_act_bf16_pack": (C.c_int, [vp, i32, vp, vp]),
     "rdm_conv3x3_act_bf16_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "rdm_conv3x3_act_bf16": (C.c_int, [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+    "rdm_stem_patches_bf16": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+    "rdm_maxpool3s2_bf16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "rdm_padavgpool2_bf16": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "rdm_f32_to_bf16_rows": (C.c_int, [vp, i32, vp, i32, i64, i32, i32, vp]),
+    "rdm_pack_conv_weight_bf16": (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     "rdm_bn_stats": (C.c_int, [vp, i32, i64, i32, vp, vp, vp]),
     "rdm_bn_finalize": (C.c_int, [vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "rdm_bn_bwd_reduce": (C.c_int, [vp, i32, vp, i32, vp, vp, i64, i32, vp, vp, vp]),

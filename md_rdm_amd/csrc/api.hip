@@ -533,6 +533,49 @@ int rdm_conv3x3_act_bf16(const void* y_act, int32_t ldy, int32_t channels_padded
   return launch_conv3x3_act_bf16(a, stream);
 }
 
+// the helper kernels of the bf16 forward as operators: the launchers the plan calls (they check nothing themselves)
+int rdm_stem_patches_bf16(const float* x_nchw, void* patches, int32_t batch, int32_t h, int32_t w, rdm_stream_t stream) {
+  RDM_CHECK_ARG(x_nchw && patches && batch > 0 && h > 0 && w > 0, "stem_patches_bf16: bad argument");
+  RDM_CHECK_ARG(((uintptr_t)x_nchw & 3) == 0 && ((uintptr_t)patches & 15) == 0, "stem_patches_bf16: patches must be 16-byte aligned");
+  RDM_CHECK_ARG((long)batch * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) < (1L << 30) && 3L * batch * h * w < (1L << 31), "stem_patches_bf16: too many pixels for 32-bit indices");
+  return launch_im2col_stem_bf16(x_nchw, patches, batch, h, w, stream);
+}
+
+static int check_nhwc_bf16(const void* p, int ld, int channels, const char* what) {
+  RDM_CHECK_ARG(p != nullptr, "%s: NULL tensor", what);
+  RDM_CHECK_ARG(channels > 0 && channels % 8 == 0 && ld >= channels && ld % 8 == 0, "%s: channels (%d) and pixel stride (%d) must be multiples of 8, stride >= channels", what, channels, ld);
+  RDM_CHECK_ARG(((uintptr_t)p & 15) == 0, "%s: tensor must be 16-byte aligned", what);
+  return 0;
+}
+
+int rdm_maxpool3s2_bf16(const void* x, void* y, int32_t ldy, int32_t batch, int32_t h, int32_t w, int32_t channels, rdm_stream_t stream) {
+  RDM_CHECK_ARG(batch > 0 && h > 0 && w > 0 && (long)batch * h * w < (1L << 30), "maxpool3s2_bf16: bad geometry");
+  if (int rc = check_nhwc_bf16(x, channels, channels, "maxpool3s2_bf16 (x)")) return rc;
+  if (int rc = check_nhwc_bf16(y, ldy, channels, "maxpool3s2_bf16 (y)")) return rc;
+  return launch_maxpool3s2_bf16(x, y, ldy, batch, h, w, channels, stream);
+}
+
+int rdm_padavgpool2_bf16(const void* x, int32_t ldx, const float* scale, const float* shift, void* out, int32_t batch, int32_t h, int32_t w, int32_t channels,
+                         rdm_stream_t stream) {
+  RDM_CHECK_ARG(batch > 0 && h > 0 && w > 0 && (long)batch * h * w < (1L << 30), "padavgpool2_bf16: bad geometry");
+  RDM_CHECK_ARG(scale && shift && (((uintptr_t)scale | (uintptr_t)shift) & 15) == 0, "padavgpool2_bf16: scale and shift must be 16-byte aligned");
+  if (int rc = check_nhwc_bf16(x, ldx, channels, "padavgpool2_bf16 (x)")) return rc;
+  if (int rc = check_nhwc_bf16(out, channels, channels, "padavgpool2_bf16 (out)")) return rc;
+  return launch_trans_pool_bf16(x, ldx, scale, shift, out, batch, h, w, channels, stream);
+}
+
+int rdm_f32_to_bf16_rows(const float* src, int32_t ld_src, void* dst, int32_t ld_dst, int64_t rows, int32_t cols, int32_t cols_pad, rdm_stream_t stream) {
+  RDM_CHECK_ARG(src && dst && rows > 0 && cols > 0 && cols_pad >= cols && ld_src >= cols && ld_dst >= cols_pad, "f32_to_bf16_rows: bad argument");
+  RDM_CHECK_ARG(((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 15) == 0 && ld_dst % 8 == 0, "f32_to_bf16_rows: dst must be 16-byte aligned, its row stride a multiple of 8");
+  return launch_f32_to_bf16_rows(src, ld_src, dst, ld_dst, rows, cols, cols_pad, stream);
+}
+
+int rdm_pack_conv_weight_bf16(const float* w_oihw, void* w_packed, int32_t out_c, int32_t in_c, int32_t ld, int32_t taps, rdm_stream_t stream) {
+  RDM_CHECK_ARG(w_oihw && w_packed && out_c > 0 && in_c > 0 && taps > 0 && ld >= in_c, "pack_conv_weight_bf16: bad argument");
+  RDM_CHECK_ARG(((uintptr_t)w_oihw & 3) == 0 && ((uintptr_t)w_packed & 15) == 0 && ld % 8 == 0, "pack_conv_weight_bf16: w_packed must be 16-byte aligned, its row stride a multiple of 8");
+  return launch_pack_w_bf16(w_oihw, w_packed, out_c, in_c, ld, taps, stream);
+}
+
 static int check_nhwc(const void* p, int ld, int channels, const char* what) {
   RDM_CHECK_ARG(p != nullptr, "%s: NULL tensor", what);
   RDM_CHECK_ARG(channels > 0 && channels % 4 == 0 && ld >= channels && ld % 4 == 0, "%s: channels (%d) and pixel stride (%d) must be multiples of 4, stride >= channels", what, channels, ld);

@@ -374,6 +374,50 @@ def row_colstats_bf16(dev):
                    scratch=dict(s=g.e(Cc, dtype=f64), q=g.e(Cc, dtype=f64)))
 
 
+# the helper kernels of the bf16 forward (tests/test_gpu_bf16_exact.py holds their values to float64 references)
+def row_stem_patches_bf16(dev):
+    g = Gen("stem_patches", dev)
+    L = _l().lib()
+    B, H, W = 2, 31, 30                                                                # 16 x 15 output pixels x 80 threads each: 150 workgroups
+    M = B * 16 * 15
+    return sp.Case(dict(x=g.n(B, 3, H, W)), lambda b, st: chk(L.rdm_stem_patches_bf16(P(b["x"]), P(b["p"]), B, H, W, st)), outs=("p",), scratch=dict(p=g.e(M, 160, dtype=bf16)))
+
+
+def row_maxpool3s2_bf16(dev):
+    g = Gen("maxpool_bf16", dev)
+    L = _l().lib()
+    B, H, W, Cc, ldy = 2, 15, 14, 96, 104
+    M = B * 8 * 7
+    return sp.Case(dict(x=g.n(B, H, W, Cc, dtype=bf16)), lambda b, st: chk(L.rdm_maxpool3s2_bf16(P(b["x"]), P(b["y"]), ldy, B, H, W, Cc, st)), outs=("y",),
+                   scratch=dict(y=g.e(M, ldy, dtype=bf16)))
+
+
+def row_padavgpool2_bf16(dev):
+    g = Gen("padavgpool_bf16", dev)
+    L = _l().lib()
+    B, H, W, Cc, ldx = 2, 15, 13, 96, 104
+    M = B * 8 * 7
+    ins = dict(x=g.n(B, H, W, ldx, dtype=bf16), sc=g.u(Cc, lo=0.5, hi=1.5), sh=g.n(Cc, scale=0.3))
+    return sp.Case(ins, lambda b, st: chk(L.rdm_padavgpool2_bf16(P(b["x"]), ldx, P(b["sc"]), P(b["sh"]), P(b["out"]), B, H, W, Cc, st)), outs=("out",),
+                   scratch=dict(out=g.e(M, Cc, dtype=bf16)))
+
+
+def row_f32_to_bf16_rows(dev):
+    g = Gen("rows_bf16", dev)
+    L = _l().lib()
+    rows, cols, cols_pad, lds, ldd = 96, 147, 160, 152, 168                            # the stem weight's conversion, in wider buffers
+    return sp.Case(dict(src=g.n(rows, lds)), lambda b, st: chk(L.rdm_f32_to_bf16_rows(P(b["src"]), lds, P(b["dst"]), ldd, rows, cols, cols_pad, st)), outs=("dst",),
+                   scratch=dict(dst=g.e(rows, ldd, dtype=bf16)))
+
+
+def row_pack_conv_weight_bf16(dev):
+    g = Gen("pack_bf16", dev)
+    L = _l().lib()
+    O, I, ld = 48, 136, 160
+    return sp.Case(dict(w=g.n(O, I, 3, 3)), lambda b, st: chk(L.rdm_pack_conv_weight_bf16(P(b["w"]), P(b["wp"]), O, I, ld, 9, st)), outs=("wp",),
+                   scratch=dict(wp=g.e(9, O, ld, dtype=bf16)))
+
+
 def _p32(c):
     return (c + 31) // 32 * 32
 
@@ -832,6 +876,11 @@ ROWS = {
     "rdm_conv3x3_act_bf16_pack": ("bf16", row_conv3x3_act_bf16_pack),
     "rdm_conv3x3_act_bf16": ("bf16", row_conv3x3_act_bf16),
     "rdm_colstats_bf16": ("bf16", row_colstats_bf16),
+    "rdm_stem_patches_bf16": ("bf16", row_stem_patches_bf16),
+    "rdm_maxpool3s2_bf16": ("bf16", row_maxpool3s2_bf16),
+    "rdm_padavgpool2_bf16": ("bf16", row_padavgpool2_bf16),
+    "rdm_f32_to_bf16_rows": ("bf16", row_f32_to_bf16_rows),
+    "rdm_pack_conv_weight_bf16": ("bf16", row_pack_conv_weight_bf16),
     "rdm_wsm_conv_bf16": ("bf16", row_wsm_conv_bf16),
     "rdm_wsm_deconv_bf16": ("bf16", row_wsm_deconv_bf16),
     "rdm_wsm_strip_bf16": ("bf16", row_wsm_strip_bf16),
