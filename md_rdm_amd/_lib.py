@@ -181,6 +181,15 @@ _EVAL_SIGNATURES = {
 }
 EVAL_ALIGN = {"none": 0, "median": 1, "logmean": 2}          # RDM_EVAL_ALIGN_* (include/rdm_eval.h)
 
+# include/rdm_optim.h: gradient accumulation, the squared global norm and the clipped AdamW step, part of librdm_hip.so, declared in a header of its own
+_OPTIM_SIGNATURES = {
+    "rdm_grad_accumulate_f32": (C.c_int, [vp, vp, i64, i32, vp]),
+    "rdm_grad_sumsq_workspace_bytes": (sz, [i64]),
+    "rdm_grad_sumsq_f64": (C.c_int, [vp, i64, vp, vp, sz, vp]),
+    "rdm_adamw_fused_clip": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, i32, f32, vp, vp]),
+}
+GRAD_ACC_COPY, GRAD_ACC_ADD, CLIP_MAX_SLOTS = 0, 1, 8        # RDM_GRAD_ACC_*, RDM_CLIP_MAX_SLOTS (include/rdm_optim.h)
+
 _lib = None
 _bench = None
 
@@ -202,7 +211,7 @@ def lib():
             raise RdmError(f"{LIB_PATH} not found - run `python -m md_rdm_amd.build` (hipcc --offload-arch=gfx950). "
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES):
+        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _OPTIM_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -251,6 +260,10 @@ def viz_symbols():
 
 def eval_symbols():
     return list(_EVAL_SIGNATURES)
+
+
+def optim_symbols():
+    return list(_OPTIM_SIGNATURES)
 
 
 def check(rc):

@@ -6,6 +6,7 @@
 #include "rdm_common.h"
 #include "elementwise.h"
 #include "xsplit_dev.h"
+#include "adamw_dev.h"
 
 namespace rdm {
 
@@ -758,31 +759,7 @@ int launch_f64_to_f32(const double* src, float* dst, int n, hipStream_t s) {
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_adamw(float* p, const float* g, float* m, float* v, long n4, long n, float lr, float b1, float b2,
                                                float eps, float wd, float bc1, float rsqrt_bc2, float gscale) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    float4 pp = ld4(p + i * 4), gg = ld4(g + i * 4), mm = ld4(m + i * 4), vv = ld4(v + i * 4);
-    float* P = &pp.x; float* Gv = &gg.x; float* Mv = &mm.x; float* Vv = &vv.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gr = Gv[k] * gscale;
-      float w = P[k] * (1.f - lr * wd);
-      Mv[k] = b1 * Mv[k] + (1.f - b1) * gr;
-      Vv[k] = b2 * Vv[k] + (1.f - b2) * gr * gr;
-      const float denom = sqrtf(Vv[k]) * rsqrt_bc2 + eps;
-      w -= (lr / bc1) * (Mv[k] / denom);
-      P[k] = w;
-    }
-    st4(p + i * 4, pp); st4(m + i * 4, mm); st4(v + i * 4, vv);
-  }
-  // tail (n not a multiple of 4)
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long i = n4 * 4 + threadIdx.x;
-    const float gr = g[i] * gscale;
-    float w = p[i] * (1.f - lr * wd);
-    m[i] = b1 * m[i] + (1.f - b1) * gr;
-    v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-    w -= (lr / bc1) * (m[i] / (sqrtf(v[i]) * rsqrt_bc2 + eps));
-    p[i] = w;
-  }
+  adamw_sweep(p, g, m, v, n4, n, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);     // the body: adamw_dev.h, shared with the clipped step (optim.hip)
 }
 
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd, int step,

@@ -136,17 +136,97 @@ def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_ou
 
 class FusedAdamW:
     """torch.optim.AdamW(lr) semantics (module.py:41) as one launch per contiguous TRAINABLE range of the model's flat parameter /
-    gradient buffers (2 for the reference's live graph) + a tiny torch step for the 4 Weights scalars."""
+    gradient buffers (2 for the reference's live graph) + a tiny torch step for the 4 Weights scalars.
 
-    def __init__(self, model: DepthEstimationNet, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
+    Gradient accumulation (Lightning's ``accumulate_grad_batches``): a window of k micro-batches is k backward passes with
+    ``accumulate_grad()`` after each but the last and ``step()`` after the last; ``zero_grad()`` opens the window.  The backward pass
+    overwrites the flat gradient buffer, so the running sum lives in a buffer of its own (allocated on first use, like the moments):
+    ``accumulate_grad()`` is acc = g after the first micro-batch and acc += g after the later ones, over the trainable ranges; the last
+    micro-batch's gradient gets g += acc just before the update, so the step reads the gradient buffer as it always does.  ``step``
+    applies 1/k for the k micro-batches actually seen (a partial window at the end of an epoch divides by what it holds).  The four
+    ``weight_layer`` scalars accumulate in their ``.grad``, as torch does.  BatchNorm running statistics are updated by EVERY micro-batch's
+    forward, as under Lightning: k micro-batches of B are k momentum updates with statistics over B samples, not one over k B.
+    Data parallel: the backward of a non-final micro-batch runs inside ``no_sync()`` and issues no collective (DDP's ``no_sync``); the final
+    one adds the accumulator per stage slice inside the stage hook, before that stage's reduction is issued (``attach_sync(sync)`` installs that
+    hook and must be called before the window's first backward pass), and the scale is 1/(k world).
+
+    ``clip`` (Lightning's ``gradient_clip_val``; None = off): clip by the global 2-norm of the scaled gradient, as
+    ``torch.nn.utils.clip_grad_norm_`` on every trainable tensor would.  One sum of squares per trainable range (rdm_grad_sumsq_f64) into
+    consecutive float64 slots, one more slot for the ``weight_layer`` gradients; the update is rdm_adamw_fused_clip, whose threads form the
+    coefficient from the slots themselves, and the small gradients are multiplied by the coefficient that kernel wrote.  Nothing is read
+    by the host: ``last_grad_norm`` (the norm before clipping) is a device scalar, and reading it is the caller's synchronisation.  Data
+    parallel: the norm must be the reduced gradient's, so clipping waits for every stage (``finish()``) and updates after the last one;
+    with the "reduce_scatter" exchange a rank holds only its shard of the sum, and ``step`` raises."""
+
+    def __init__(self, model: DepthEstimationNet, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, clip=None):
         self.model, self.lr, self.betas, self.eps, self.wd = model, lr, betas, eps, weight_decay
         self.step_count = 0
         self.m = self.v = None
         self.sync, self.mode = None, "after the last stage"        # data parallel: set by step(sync=...)
         self.small = torch.optim.AdamW([p for p in model.weight_layer.parameters() if p.requires_grad], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if clip is not None and not float(clip) >= 0.0:
+            raise ValueError(f"FusedAdamW: clip must be None or a non-negative norm (got {clip!r})")
+        self.clip = clip
+        self.acc = None                                            # the running gradient sum of an accumulation window
+        self.micro = 0                                             # micro-batches held by acc
+        self.last_grad_norm = None                                 # device scalar (float64): the global norm the last clipped step saw
+        self._folded = self._no_sync = False
+        self._hooked = None
+        self._slots = self._coef = self._sumsq_ws = None
 
     def zero_grad(self):
+        """Opens a window: clears the ``weight_layer`` gradients and forgets whatever the accumulator holds."""
         self.small.zero_grad(set_to_none=True)
+        self.micro, self._folded = 0, False
+
+    # ---- gradient accumulation ----
+    def _accumulate(self, dst, src, a, b, mode):
+        """dst = src (mode 0) / dst += src (mode 1) on the trainable parts of the flat element range [a, b)"""
+        from . import _lib
+        L, st = _lib.lib(), _lib.stream()
+        for ta, tb in self.trainable_ranges():
+            lo, hi = max(a, ta), min(b, tb)
+            if lo < hi:
+                _lib.check(L.rdm_grad_accumulate_f32(C.c_void_p(dst.data_ptr() + 4 * lo), C.c_void_p(src.data_ptr() + 4 * lo), hi - lo, mode, st))
+
+    def accumulate_grad(self):
+        """After the backward pass of a micro-batch that is NOT the last of its window: the flat gradient joins the accumulator."""
+        from . import _lib
+        flat, gflat, _ = self.model._flat
+        if self.acc is None or self.acc.numel() != gflat.numel() or self.acc.device != gflat.device:
+            self.acc = torch.zeros_like(gflat)
+        self._accumulate(self.acc, gflat, 0, gflat.numel(), _lib.GRAD_ACC_COPY if self.micro == 0 else _lib.GRAD_ACC_ADD)
+        self.micro += 1
+
+    def no_sync(self):
+        """Context for the backward pass of a non-final micro-batch under data parallelism: the stage hook issues no collective."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            prev, self._no_sync = self._no_sync, True
+            try:
+                yield self
+            finally:
+                self._no_sync = prev
+        return scope()
+
+    def attach_sync(self, sync):
+        """Put this optimiser's stage hook in front of the exchange's (``parallel.attach`` installed ``sync.on_stage``): silent inside
+        ``no_sync()``, and on the window's last micro-batch it adds the accumulator to the stage's slice before the reduction is issued."""
+        if sync is None or sync.world <= 1 or self._hooked is sync:
+            return
+        self.sync, self._hooked = sync, sync
+
+        def hook(stage):
+            if self._no_sync:
+                return
+            if self.micro:
+                a, b = sync.slices[stage]
+                self._accumulate(self.model._flat[1], self.acc, a, b, 1)
+                self._folded = True
+            sync.on_stage(stage)
+        self.model.grad_ready_hook = hook
 
     def trainable_ranges(self):
         """Maximal contiguous [start, stop) element ranges of the flat buffer that hold tensors which receive a gradient.
@@ -168,33 +248,90 @@ class FusedAdamW:
             self._ranges, self._ranges_key = [(a, b) for a, b, _ in ranges], key
         return self._ranges
 
-    def _update(self, a, b, grad_scale):
-        """AdamW on the trainable parts of the flat element range [a, b) (one launch per contiguous trainable piece)."""
+    def _update(self, a, b, grad_scale, clip=None, n_slots=0):
+        """AdamW on the trainable parts of the flat element range [a, b) (one launch per contiguous trainable piece); with ``clip`` the
+        clipped step, its coefficient formed in the kernel from the first ``n_slots`` slots."""
         from . import _lib
         flat, gflat, _ = self.model._flat
         L, st = _lib.lib(), _lib.stream()
         off = C.c_void_p
         for ta, tb in self.trainable_ranges():
             lo, hi = max(a, ta), min(b, tb)
-            if lo < hi:
+            if lo < hi and clip is None:
                 _lib.check(L.rdm_adamw_fused(off(flat.data_ptr() + 4 * lo), off(gflat.data_ptr() + 4 * lo), off(self.m.data_ptr() + 4 * lo),
                                              off(self.v.data_ptr() + 4 * lo), hi - lo, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
                                              self.step_count, float(grad_scale), st))
+            elif lo < hi:
+                _lib.check(L.rdm_adamw_fused_clip(off(flat.data_ptr() + 4 * lo), off(gflat.data_ptr() + 4 * lo), off(self.m.data_ptr() + 4 * lo),
+                                                  off(self.v.data_ptr() + 4 * lo), hi - lo, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                                                  self.step_count, float(grad_scale), _lib.ptr(self._slots), n_slots, float(clip), _lib.ptr(self._coef), st))
 
-    def step(self, grad_scale=1.0, sync=None):
+    def _norm_slots(self, grad_scale, small_grads):
+        """Sum of squares of the UNSCALED flat gradient per trainable range into consecutive slots, one more slot for the small gradients
+        (already final, so divided by grad_scale^2 to stand beside the others); sets ``last_grad_norm``.  -> the number of slots."""
+        from . import _lib
+        gflat = self.model._flat[1]
+        L, st = _lib.lib(), _lib.stream()
+        ranges = self.trainable_ranges()
+        if len(ranges) + 1 > _lib.CLIP_MAX_SLOTS:
+            raise _lib.RdmError(f"FusedAdamW(clip=...): {len(ranges)} trainable ranges + 1 exceed the {_lib.CLIP_MAX_SLOTS} norm slots of rdm_adamw_fused_clip")
+        need = max(int(L.rdm_grad_sumsq_workspace_bytes(b - a)) for a, b in ranges)
+        if self._slots is None or self._slots.device != gflat.device or self._sumsq_ws.numel() * 8 < need:
+            self._slots = torch.zeros(_lib.CLIP_MAX_SLOTS, dtype=torch.float64, device=gflat.device)
+            self._coef = torch.ones(1, dtype=torch.float32, device=gflat.device)
+            self._sumsq_ws = torch.empty(need // 8, dtype=torch.float64, device=gflat.device)
+        for i, (a, b) in enumerate(ranges):                        # (the launches of one stream run in order: the ranges share the workspace)
+            _lib.check(L.rdm_grad_sumsq_f64(C.c_void_p(gflat.data_ptr() + 4 * a), b - a, C.c_void_p(self._slots.data_ptr() + 8 * i), _lib.ptr(self._sumsq_ws),
+                                            self._sumsq_ws.numel() * 8, st))
+        n = len(ranges)
+        if small_grads:
+            self._slots[n] = torch.stack([g.detach().double().square().sum() for g in small_grads]).sum() / (float(grad_scale) ** 2)
+            n += 1
+        self.last_grad_norm = self._slots[:n].sum().sqrt() * abs(float(grad_scale))
+        return n
+
+    @staticmethod
+    def _scale_small(grads, factor):
+        for g in grads:                                            # the weight_layer scalars: a handful of one-element launches
+            g.mul_(factor)
+
+    def step(self, grad_scale=1.0, sync=None, clip=None):
         """``sync`` = the GradSync of a data-parallel run: the update then runs PER BUCKET as each stage's reduction lands
         (``GradSync.finish(on_reduced=...)``: stage k's wait is a stream dependency and its AdamW launch follows at once, under the
         reductions still in flight; with the "reduce_scatter" exchange on this rank's shard only, the updated parameters are
         all-gathered).  Without it: the monolithic update of the whole buffer with the given ``grad_scale`` (what one process runs:
-        2 launches for the reference's live graph, around d_1.conv1)."""
+        2 launches for the reference's live graph, around d_1.conv1).
+        After k - 1 calls of ``accumulate_grad()`` the gradient is the window's sum and the scale ``grad_scale`` / k (/ world under data
+        parallelism).  ``clip``: this step's clipping norm (None: the constructor's); see the class text.  With neither, the launches are
+        exactly those of the plain step."""
+        from . import _lib
         flat, gflat, _ = self.model._flat
         if self.m is None or self.m.data_ptr() == 0 or self.m.numel() != flat.numel():
             self.m = torch.zeros_like(flat)
             self.v = torch.zeros_like(flat)
+        clip = self.clip if clip is None else clip
+        if clip is not None and not float(clip) >= 0.0:
+            raise ValueError(f"FusedAdamW.step: clip must be a non-negative norm (got {clip!r})")
+        dp = sync is not None and sync.world > 1
+        if dp and clip is not None and sync.exchange == "reduce_scatter":
+            raise _lib.RdmError("FusedAdamW: gradient clipping with the 'reduce_scatter' exchange is not built - a rank holds one shard of the reduced "
+                                "gradient, so its norm is not the global norm; use the 'all_reduce' exchange")
+        k = self.micro + 1                                         # micro-batches in this window
+        if dp and k > 1 and self._hooked is not sync:
+            raise _lib.RdmError("FusedAdamW: gradient accumulation under data parallelism needs attach_sync(sync) before the window's first backward pass "
+                                "(the stage hook must stay silent on the non-final micro-batches and add the accumulator before the last one's reductions)")
+        if self.micro and not self._folded:                        # one process (or no stage hook): the window's sum, just before the update
+            self._accumulate(gflat, self.acc, 0, gflat.numel(), _lib.GRAD_ACC_ADD)
+        self.micro, self._folded = 0, False
         self.step_count += 1
-        if sync is not None and sync.world > 1:
-            self.sync, self.mode = sync, "per stage, as its reduction lands"
-            scale = 1.0 / sync.world
+        small_grads = [p.grad for g in self.small.param_groups for p in g["params"] if p.grad is not None]
+        if dp:
+            self.sync = sync
+            scale = float(grad_scale) / (k * sync.world)
+        else:
+            scale = float(grad_scale) / k if k > 1 else grad_scale
+        if dp and clip is None:
+            self.mode = "per stage, as its reduction lands"
             covered = []
 
             def on_reduced(stage, ranges):
@@ -204,9 +341,19 @@ class FusedAdamW:
             sync.finish(on_reduced=on_reduced)
             # parameters outside every stage bucket (none for the reference's graph: the stages tile the stack) would be stale replicas
             assert sum(b - a for a, b in covered) >= sum(b - a for a, b in self.trainable_ranges()), "backward stages do not cover the trainable parameters"
+            if k > 1:
+                self._scale_small(small_grads, 1.0 / k)          # finish() left the rank mean of the window's sum
         else:
+            if dp:                                                 # the norm is the REDUCED gradient's: every stage first, one update after the last
+                self.mode = "after the last stage"
+                sync.finish()
+            if k > 1:
+                self._scale_small(small_grads, 1.0 / k)
+            n_slots = self._norm_slots(scale, small_grads) if clip is not None else 0
             for a, b in self.trainable_ranges():                  # 2 launches for the reference's live graph (around d_1.conv1)
-                self._update(a, b, grad_scale)
+                self._update(a, b, scale, clip, n_slots)
+            if clip is not None and small_grads:
+                self._scale_small(small_grads, self._coef[0])    # the coefficient the kernel formed from the same slots
         self.model.mark_weights_changed(relative_decoders=False)  # derived bf16 copies are stale now (d_6..d_10 are not in the flat buffer: untouched)
         self.small.step()
 
@@ -228,6 +375,55 @@ class FusedAdamW:
         self.small.load_state_dict(sd["small"])
         for g in self.small.param_groups:
             g["lr"] = self.lr
+
+
+def accumulation_windows(batches, k):
+    """``batches`` cut into windows of ``k``: yields (batch, index in its window, last of its window).  One batch is held ahead, so the last
+    batch of the iterable closes its window even when the window is not full (the epoch-end flush)."""
+    if k < 1:
+        raise ValueError(f"accumulation_windows: k = {k} must be at least 1")
+    it = iter(batches)
+    try:
+        cur = next(it)
+    except StopIteration:
+        return
+    i = 0
+    while True:
+        try:
+            nxt, more = next(it), True
+        except StopIteration:
+            nxt, more = None, False
+        last = i == k - 1 or not more
+        yield cur, i, last
+        if not more:
+            return
+        cur, i = nxt, 0 if last else i + 1
+
+
+def train_epoch(model, opt, batches, accumulate=1, sync=None, on_step=None, step_fn=None):
+    """One pass over ``batches`` with an optimiser step per window of ``accumulate`` batches (module.py:64-97 under Lightning's
+    ``accumulate_grad_batches``): ``zero_grad`` opens a window, the backward pass of every batch but the window's last runs inside
+    ``opt.no_sync()`` and is followed by ``opt.accumulate_grad()``, the last one by ``opt.step(sync=sync)``, which divides by the batches the
+    window actually holds.  ``on_step(step index, batches in the window, loss, parts)`` is called after every optimiser step with the losses of
+    the window's last batch.  ``accumulate=1`` is the plain loop: zero_grad, training_step, backward, step.  -> optimiser steps taken."""
+    step_fn = step_fn or training_step
+    steps = 0
+    for (x, y), i, last in accumulation_windows(batches, accumulate):
+        if i == 0:
+            opt.zero_grad()
+        if last:
+            loss, parts = step_fn(model, x, y)
+            loss.backward()
+            opt.step(sync=sync)
+            if on_step is not None:
+                on_step(steps, i + 1, loss, parts)
+            steps += 1
+        else:
+            with opt.no_sync():
+                loss, parts = step_fn(model, x, y)
+                loss.backward()
+            opt.accumulate_grad()
+    return steps
 
 
 def find_learning_rate(model, opt, batches, min_lr=1e-8, max_lr=1.0, num_training=100, early_stop_threshold=4.0, beta=0.98, sync=None):

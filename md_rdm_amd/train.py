@@ -48,7 +48,7 @@ class ReduceLROnPlateau:
         self.best, self.bad = sd["best"], sd["bad"]
 
 
-def main(argv=None):
+def build_parser():
     parser = ArgumentParser("Trains mono depth estimation models (MI355X-native stack)")
     parser.add_argument("--seed", default=None, type=int)
     parser.add_argument("--precision", default=32, type=int, help="32 (default here - the parity configuration): float32 training and validation; 16 (the reference's default, AMP O2, train.py:11,57-58): training in the mixed-precision "
@@ -76,7 +76,20 @@ def main(argv=None):
     parser.add_argument("--relative_decoders", type=int, nargs="*", default=[], help="subset of 6 7 8 9 10: the relative decoders the reference keeps commented out (RDM_Net.py:57-61)")
     parser.add_argument("--relative_bf16", action="store_true", help="training-mode forward of the relative decoders (--relative_decoders) on the bf16 MFMA path: bf16 conv operands, "
                         "float32 BatchNorm from batch statistics (DepthEstimationNet.set_relative_train_precision('bf16')); independent of --precision")
-    args = parser.parse_args(argv)
+    parser.add_argument("--accumulate_grad_batches", type=int, default=1, help="K (Lightning's name): one optimiser step per K batches, on the mean of their gradients "
+                        "(harness.FusedAdamW.accumulate_grad); a partial window at the end of an epoch is stepped with what it holds; BatchNorm running statistics "
+                        "still update on every batch")
+    parser.add_argument("--gradient_clip_val", type=float, default=0.0, help="V (Lightning's name): clip the gradient's global 2-norm to V before every optimiser step "
+                        "(torch.nn.utils.clip_grad_norm_ semantics, inside the fused AdamW launch); 0 (default) = off")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.accumulate_grad_batches < 1:
+        raise SystemExit(f"--accumulate_grad_batches must be at least 1 (got {args.accumulate_grad_batches})")
+    if not args.gradient_clip_val >= 0:
+        raise SystemExit(f"--gradient_clip_val must be non-negative, 0 = off (got {args.gradient_clip_val})")
     if args.precision not in (16, 32):
         raise SystemExit("--precision must be 16 or 32")
     if not args.synthetic and not args.nyu_path:
@@ -127,7 +140,13 @@ def main(argv=None):
     model.flatten_parameters()
     sync = parallel.attach(model)
     best_delta1, best_path = None, None
-    opt = harness.FusedAdamW(model, lr=args.learning_rate)
+    clip = args.gradient_clip_val if args.gradient_clip_val > 0 else None
+    if clip is not None and sync.world > 1 and sync.exchange == "reduce_scatter":
+        raise SystemExit("--gradient_clip_val with the reduce_scatter exchange is not built (a rank holds one shard of the reduced gradient, not its global norm): "
+                         "use the all_reduce exchange")
+    opt = harness.FusedAdamW(model, lr=args.learning_rate, clip=clip)
+    opt.attach_sync(sync)                                        # data parallel: no exchange on the non-final micro-batches of a window
+    K = args.accumulate_grad_batches
     sched = ReduceLROnPlateau(opt, "max", patience=2)
     start_epoch = 0
     if resumed is not None:
@@ -179,14 +198,13 @@ def main(argv=None):
         model.train()
         model.set_precision("f32")
         t0 = time.time()
-        for it, (x, y) in enumerate(train_batches(epoch)):
-            opt.zero_grad()
-            loss, parts = harness.training_step(model, x, y)
-            loss.backward()
-            opt.step(sync=sync)                                  # per bucket as its reduction lands (one process: the plain update)
+        def report(it, seen, loss, parts):                       # once per OPTIMISER step: the losses of the window's last micro-batch
             if rank == 0:
+                norm = f" grad_norm {opt.last_grad_norm.item():.4f}" if clip is not None else ""
                 print(f"epoch {epoch} step {it} loss {loss.item():.4f} MSE {parts['mse'].item():.4f} Ord_Loss {parts['ord_loss'].item():.4f} "
-                      f"Fine_Detail {parts['fine_detail_loss'].item():.4f}", flush=True)
+                      f"Fine_Detail {parts['fine_detail_loss'].item():.4f}{norm}", flush=True)
+        # per bucket as its reduction lands (one process: the plain update); K > 1: a step per window of K batches
+        harness.train_epoch(model, opt, train_batches(epoch), accumulate=K, sync=sync, on_step=report)
         torch.cuda.synchronize()
         model.eval()
         model.set_precision("bf16" if args.precision == 16 else "f32")
@@ -218,7 +236,7 @@ def main(argv=None):
             from .checkpoint import to_lightning
             os.makedirs(args.checkpoint_dir, exist_ok=True)
             path = os.path.join(args.checkpoint_dir, f"epoch={epoch}-val_delta1={d1:.4f}.ckpt")
-            torch.save(to_lightning(model, {"epoch": epoch, "global_step": (epoch + 1) * steps, "best_val_delta1": d1}, optimizer=opt, scheduler=sched), path)
+            torch.save(to_lightning(model, {"epoch": epoch, "global_step": (epoch + 1) * -(-steps // K), "best_val_delta1": d1}, optimizer=opt, scheduler=sched), path)
             if best_path and best_path != path and os.path.exists(best_path):
                 os.remove(best_path)
             best_delta1, best_path = d1, path
