@@ -37,6 +37,7 @@ size_t rdm_eval_standard_workspace_bytes(int32_t batch, int32_t h, int32_t w);
  *  6. pred_out, when given: q at EVERY pixel of the frame, valid or not; for a sample whose row is zeros or NaN it is formed with s = 1.
  * One launch; the workgroups never wait for each other; plain stores, no floating-point atomics, no memset: a repeated call gives the same
  * bytes, and a sample alone gives the row it gives inside a batch.  Any h, w >= 1 up to a plane of 2^31 - 1 elements.
+ * The map is taken to cover the WHOLE depth frame; rdm_eval_view.h declares the same call for a map that covers a rectangle of it.
  * RDM_ERR_BAD_ARGUMENT (nothing is written): log_map, depth, rows or workspace NULL; log_map, rows, workspace or pred_out not 8-byte aligned,
  * depth not aligned to its element; a non-positive size, a plane beyond 2^31 - 1 elements,
  * an unknown align, !(0 <= min_depth < max_depth), an empty or out-of-frame crop, workspace_bytes below

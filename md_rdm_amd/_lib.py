@@ -181,6 +181,11 @@ _EVAL_SIGNATURES = {
 }
 EVAL_ALIGN = {"none": 0, "median": 1, "logmean": 2}          # RDM_EVAL_ALIGN_* (include/rdm_eval.h)
 
+# include/rdm_eval_view.h: the same evaluation for a map that covers a rectangle of the depth frame, declared in a header of its own
+_EVAL_VIEW_SIGNATURES = {
+    "rdm_eval_standard_view_f64": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, f64, f64, C.POINTER(i32), C.POINTER(f64), vp, vp, vp, sz, vp]),
+}
+
 # include/rdm_optim.h: gradient accumulation, the squared global norm and the clipped AdamW step, part of librdm_hip.so, declared in a header of its own
 _OPTIM_SIGNATURES = {
     "rdm_grad_accumulate_f32": (C.c_int, [vp, vp, i64, i32, vp]),
@@ -211,7 +216,7 @@ def lib():
             raise RdmError(f"{LIB_PATH} not found - run `python -m md_rdm_amd.build` (hipcc --offload-arch=gfx950). "
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _OPTIM_SIGNATURES):
+        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -260,6 +265,10 @@ def viz_symbols():
 
 def eval_symbols():
     return list(_EVAL_SIGNATURES)
+
+
+def eval_view_symbols():
+    return list(_EVAL_VIEW_SIGNATURES)
 
 
 def optim_symbols():

@@ -5,7 +5,7 @@
 //
 // Grid (B): one workgroup of 1024 threads per sample, so nothing is exchanged between workgroups.  Thread t owns the pixels t, t + 1024, ...
 // in EVERY pass, so what it stored to the workspace in the first pass it reads back itself.  Passes over the sample:
-//   A  p = exp(bicubic(map)) -> workspace; valid count, any non-finite p, sum ln d, sum ln p
+//   A  p = exp(bicubic(map)) -> workspace (the map covers a VIEW of the depth frame, the whole frame unless the caller says otherwise); valid count, any non-finite p, sum ln d, sum ln p
 //   M  median alignment only: an exact radix select of the middle order statistic of d_valid and of p_valid at once.  The bit patterns of
 //      non-negative doubles sort like the doubles: eight passes of 8-bit digits from the top, an integer histogram per array in LDS (integer
 //      atomics: the counts do not depend on the order), a scan of the 256 bins, the bin that holds the wanted rank extends the key prefix.
@@ -13,9 +13,12 @@
 //      key above it: one more pass with an integer minimum.
 //   B  q = clamp(s * p) -> pred_out; the sums, in a fixed order (a thread's pixels front to back, lanes by shuffle, wavefronts in sequence)
 // Plain stores only, no floating-point atomics: a repeated call gives the same bytes, a sample alone the row it gives inside a batch.
+#include <cmath>
+
 #include "rdm_common.h"
 #include "postproc_dev.h"
 #include "../../include/rdm_eval.h"
+#include "../../include/rdm_eval_view.h"
 
 namespace rdm {
 
@@ -35,6 +38,10 @@ struct EsArgs {
   int h, w, align, has_crop;
   int y0, x0, y1, x1;
   double lo, hi;
+  // the view: the map's rows cover the depth rows [vy0, vy0 + 128 / sy), its columns [vx0, vx0 + 128 / sx); the full frame is (0, 0, 128 / h, 128 / w),
+  // whose sy and (y + 0.5) - 0 are the operands of cubic_index(y, 128, h).  identity: a 128x128 frame under the full view reads the map as it is
+  double sy, sx, vy0, vx0;
+  int identity;
 };
 
 struct EsState {
@@ -160,14 +167,13 @@ __global__ __launch_bounds__(ES_THREADS) void k_eval_standard(EsArgs a) {
   const double* map = a.map + (long)b * ES_SIDE * ES_SIDE;
   double* wp = a.ws + (long)b * P;
   double* row = a.rows + (long)b * ES_COLS;
-  const bool identity = a.h == ES_SIDE && a.w == ES_SIDE;
 
   // A. the prediction at the depth's resolution; what the alignment needs of the valid pixels
   double cnt = 0, sld = 0, slp = 0;
   int bad = 0;
   for (long i = tid; i < P; i += ES_THREADS) {
     const int oy = (int)((unsigned)i / (unsigned)a.w), ox = (int)((unsigned)i - (unsigned)oy * (unsigned)a.w);
-    const double p = exp(identity ? map[i] : bicubic_at(map, ES_SIDE, ES_SIDE, a.h, a.w, oy, ox));
+    const double p = exp(a.identity ? map[i] : bicubic_at_view(map, ES_SIDE, ES_SIDE, a.sy, a.sx, ((double)oy + 0.5) - a.vy0, ((double)ox + 0.5) - a.vx0));
     wp[i] = p;
     double dv;
     if (es_valid(d, i, a, dv)) {
@@ -251,9 +257,10 @@ extern "C" size_t rdm_eval_standard_workspace_bytes(int32_t batch, int32_t h, in
   return es_plane_ok(batch, h, w) ? (size_t)batch * (size_t)h * (size_t)w * sizeof(double) : 0;
 }
 
-extern "C" int rdm_eval_standard_f64(const double* log_map, const void* depth, int32_t depth_is_f64, int32_t batch, int32_t h, int32_t w, int32_t align,
-                                     double min_depth, double max_depth, const int32_t* crop, double* rows, void* pred_out, void* workspace,
-                                     size_t workspace_bytes, rdm_stream_t stream) {
+// both entry points: the checks, then the one launch.  view NULL = the full frame (0, 0, h, w)
+static int es_run(const double* log_map, const void* depth, int32_t depth_is_f64, int32_t batch, int32_t h, int32_t w, int32_t align, double min_depth,
+                  double max_depth, const int32_t* crop, const double* view, double* rows, void* pred_out, void* workspace, size_t workspace_bytes,
+                  rdm_stream_t stream) {
   RDM_CHECK_ARG(log_map && depth && rows && workspace, "eval_standard: log_map, depth, rows and workspace must not be NULL");
   RDM_CHECK_ARG(((uintptr_t)log_map | (uintptr_t)rows | (uintptr_t)workspace | (uintptr_t)pred_out) % sizeof(double) == 0 &&
                     (uintptr_t)depth % (depth_is_f64 ? sizeof(double) : sizeof(float)) == 0,
@@ -267,15 +274,33 @@ extern "C" int rdm_eval_standard_f64(const double* log_map, const void* depth, i
                 crop ? (int)crop[1] : 0, crop ? (int)crop[3] : 0, (int)h, (int)w);
   RDM_CHECK_ARG(workspace_bytes >= rdm_eval_standard_workspace_bytes(batch, h, w), "eval_standard: workspace of %zu bytes, %zu needed", workspace_bytes,
                 rdm_eval_standard_workspace_bytes(batch, h, w));
+  RDM_CHECK_ARG(!view || (std::isfinite(view[0]) && std::isfinite(view[1]) && std::isfinite(view[2]) && std::isfinite(view[3]) && view[2] > 0 && view[3] > 0),
+                "eval_standard: view (%g, %g, %g, %g) must be finite with vh > 0 and vw > 0", view ? view[0] : 0.0, view ? view[1] : 0.0, view ? view[2] : 0.0,
+                view ? view[3] : 0.0);
+  const double vy0 = view ? view[0] : 0.0, vx0 = view ? view[1] : 0.0, vh = view ? view[2] : (double)h, vw = view ? view[3] : (double)w;
   EsArgs a;
   a.map = log_map, a.depth = depth, a.rows = rows, a.pred_out = (double*)pred_out, a.ws = (double*)workspace;
   a.h = h, a.w = w, a.align = align, a.has_crop = crop ? 1 : 0;
   a.y0 = crop ? crop[0] : 0, a.x0 = crop ? crop[1] : 0, a.y1 = crop ? crop[2] : h, a.x1 = crop ? crop[3] : w;
   a.lo = min_depth, a.hi = max_depth;
+  a.sy = (double)ES_SIDE / vh, a.sx = (double)ES_SIDE / vw, a.vy0 = vy0, a.vx0 = vx0;
+  a.identity = h == ES_SIDE && w == ES_SIDE && vy0 == 0.0 && vx0 == 0.0 && vh == (double)h && vw == (double)w;
   if (depth_is_f64)
     hipLaunchKernelGGL(k_eval_standard<double>, dim3(batch), dim3(ES_THREADS), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(k_eval_standard<float>, dim3(batch), dim3(ES_THREADS), 0, (hipStream_t)stream, a);
   RDM_LAUNCH_OK();
   return RDM_OK;
+}
+
+extern "C" int rdm_eval_standard_f64(const double* log_map, const void* depth, int32_t depth_is_f64, int32_t batch, int32_t h, int32_t w, int32_t align,
+                                     double min_depth, double max_depth, const int32_t* crop, double* rows, void* pred_out, void* workspace,
+                                     size_t workspace_bytes, rdm_stream_t stream) {
+  return es_run(log_map, depth, depth_is_f64, batch, h, w, align, min_depth, max_depth, crop, nullptr, rows, pred_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rdm_eval_standard_view_f64(const double* log_map, const void* depth, int32_t depth_is_f64, int32_t batch, int32_t h, int32_t w, int32_t align,
+                                          double min_depth, double max_depth, const int32_t* crop, const double* view, double* rows, void* pred_out,
+                                          void* workspace, size_t workspace_bytes, rdm_stream_t stream) {
+  return es_run(log_map, depth, depth_is_f64, batch, h, w, align, min_depth, max_depth, crop, view, rows, pred_out, workspace, workspace_bytes, stream);
 }

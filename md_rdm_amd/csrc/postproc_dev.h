@@ -69,11 +69,24 @@ __device__ __forceinline__ double dot4(const double (&v)[4], const double (&w)[4
   return __builtin_fma(v[3], w[3], acc);
 }
 
-// align_corners=False, no antialias, border indices clamped.  T = double, or float widened on load (exact): the arithmetic is float64 either way
+// cubic_index for an output grid that covers only a VIEW of the source: output sample i of a grid whose samples [v0, v0 + vn) span the n_in
+// source samples sits at real = fma(scale, pos, -0.5) with scale = n_in / vn and pos = (i + 0.5) - v0, both formed by the caller.  v0 = 0 and
+// vn = n_out make scale and pos the two operands of cubic_index's fma, so the result is cubic_index's bit for bit.  real may lie far outside
+// [0, n_in) (a sample outside the view): the float floor is held inside the range of a long before the conversion (a NaN becomes the lower
+// end), which changes nothing for a |real| below 2^62; the caller clamps the taps.
+__device__ __forceinline__ long cubic_index_view(double scale, double pos, int n_in, double& t) {
+#pragma clang fp contract(off)
+  const double real = __builtin_fma(scale, pos, -0.5);
+  const float fl = fminf(fmaxf(floorf((float)real), -0x1p62f), 0x1p62f);
+  const long idx = min((long)fl, (long)n_in - 1);
+  t = fmin(fmax(real - (double)idx, 0.0), 1.0);
+  return idx;
+}
+
+// the 4x4 taps around (iy, ix), border indices clamped: rows along x first, then the 4 rows along y
 template <typename T>
-__device__ __forceinline__ double bicubic_at(const T* __restrict__ src, int h, int w, int oh, int ow, int oy, int ox) {
-  double ty, tx, cy[4], cx[4], rows[4];
-  const int iy = cubic_index(oy, h, oh, ty), ix = cubic_index(ox, w, ow, tx);
+__device__ __forceinline__ double bicubic_taps(const T* __restrict__ src, int h, int w, int iy, double ty, int ix, double tx) {
+  double cy[4], cx[4], rows[4];
   cubic_coeffs(ty, cy);
   cubic_coeffs(tx, cx);
 #pragma unroll
@@ -85,6 +98,24 @@ __device__ __forceinline__ double bicubic_at(const T* __restrict__ src, int h, i
     rows[i] = dot4(v, cx);
   }
   return dot4(rows, cy);
+}
+
+// align_corners=False, no antialias, border indices clamped.  T = double, or float widened on load (exact): the arithmetic is float64 either way
+template <typename T>
+__device__ __forceinline__ double bicubic_at(const T* __restrict__ src, int h, int w, int oh, int ow, int oy, int ox) {
+  double ty, tx;
+  const int iy = cubic_index(oy, h, oh, ty), ix = cubic_index(ox, w, ow, tx);
+  return bicubic_taps(src, h, w, iy, ty, ix, tx);
+}
+
+// bicubic_at for an output frame of which the source covers only the view (vy0, vx0, h / sy, w / sx): py = (oy + 0.5) - vy0, px likewise
+// (cubic_index_view).  An index below -3 has all four taps on the source's first row / column, as -3 has: held there, the int arithmetic of
+// the taps cannot overflow, and t keeps the value formed from the real index.  Outside the view the source's edge is replicated.
+template <typename T>
+__device__ __forceinline__ double bicubic_at_view(const T* __restrict__ src, int h, int w, double sy, double sx, double py, double px) {
+  double ty, tx;
+  const long iy = cubic_index_view(sy, py, h, ty), ix = cubic_index_view(sx, px, w, tx);
+  return bicubic_taps(src, h, w, (int)max(iy, -3L), ty, (int)max(ix, -3L), tx);
 }
 
 // sum over the workgroup in a FIXED order (lanes by shuffle, then the wavefronts in sequence), broadcast to every thread

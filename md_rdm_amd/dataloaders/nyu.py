@@ -103,6 +103,33 @@ def identity_params(in_hw, resize, output_size):
     return make_params(1.0, 0.0, False, [], in_hw, resize, output_size)
 
 
+def test_view(in_hw):
+    """The rectangle (vy0, vx0, vh, vw) of the RAW (H, W) frame, in raw-pixel units, that the network input of ``test_params`` covers: the
+    480x640 centre crop of the frame resized to (h1, w1), mapped back through that resize (whose pixel edges divide the frame evenly); the last
+    Resize changes the sampling, not the extent.  (480, 640) -> (9.6, 13 * 640 / 666, 460.8, 640 * 640 / 666).  The ``view`` of
+    ``metrics.StandardMetrics`` / rdm_eval_standard_view_f64 when the raw depth is scored."""
+    H, W = in_hw
+    h1, w1 = resized_hw(H, W, 500)
+    if h1 < 480 or w1 < 640:
+        raise ValueError(f"CenterCrop((480, 640)) larger than the resized image {(h1, w1)}")
+    top, left = int(round((h1 - 480) / 2.0)), int(round((w1 - 640) / 2.0))
+    return (top * H / h1, left * W / w1, 480 * H / h1, 640 * W / w1)
+
+
+def val_view(in_hw, resize, output_size):
+    """``test_view`` for ``identity_params``: the (oh, ow) centre crop of the frame resized to (h1, w1) = resized_hw(H, W, resize)."""
+    H, W = in_hw
+    h1, w1 = resized_hw(H, W, resize)
+    oh, ow = output_size
+    if h1 < oh or w1 < ow:
+        raise ValueError(f"centre crop {tuple(output_size)} larger than the resized image {(h1, w1)}")
+    top, left = int(round((h1 - oh) / 2.0)), int(round((w1 - ow) / 2.0))
+    return (top * H / h1, left * W / w1, oh * H / h1, ow * W / w1)
+
+
+test_view.__test__ = False            # (a name pytest would collect from a module that imports it)
+
+
 def draw_training_params(rng, in_hw, resize=250, output_size=(228, 304)):
     """The reference's draws (nyu_dataloader.py:241,247,252,264; ColorJitter(0.4, 0.4, 0.4) shuffles its three ops)."""
     s = float(rng.uniform(1.0, 1.5))
@@ -190,11 +217,17 @@ class PrefetchLoader:
     """Iterate (x, y) training / validation batches: a reader thread fills pinned staging buffers one batch ahead, the
     H2D copies run on a dedicated copy stream, and the augmentation kernels run on the consumer's stream after an event wait."""
 
-    def __init__(self, dataset, batch_size, shuffle=None, seed=0, device="cuda", drop_last=True, rank=0, world=1, workers=0, indices=None):
+    def __init__(self, dataset, batch_size, shuffle=None, seed=0, device="cuda", drop_last=True, rank=0, world=1, workers=0, indices=None, native_depth=False):
         """``workers`` (the reference's ``--worker``, module.py:19-27 DataLoader(num_workers=...)): threads that decode the raw samples of a
         batch in parallel (h5 / npz reads release the GIL); 0 = decode in the reader thread.  The augmentation itself runs on the GPU.
         ``indices`` (evaluation): the samples to visit, in that order and never shuffled; rank r takes ``indices[r::world]`` and NO sample is
-        dropped to equalise the shards (there is no collective inside an evaluation pass).  None: the whole dataset in equal shards."""
+        dropped to equalise the shards (there is no collective inside an evaluation pass).  None: the whole dataset in equal shards.
+        ``native_depth`` (val / test only): yield ``(x, depth)`` with ``depth`` the RAW depth as uploaded, (B,1,H,W) float32, untouched by the
+        transform, for scoring at the ground truth's own resolution; ``self.view`` is then the rectangle of that frame which ``x`` covers
+        (``test_view`` / ``val_view``; None until the first batch has been read, and the current batch's from then on)."""
+        if native_depth and dataset.split == "train":
+            raise ValueError("PrefetchLoader: native_depth is for the val and test splits; the training transform rotates and scales the depth")
+        self.native_depth, self.view = bool(native_depth), None
         self.ds, self.bs, self.device = dataset, batch_size, torch.device(device)
         self.pool = None
         if workers and workers > 0:
@@ -270,4 +303,9 @@ class PrefetchLoader:
             torch.cuda.current_stream().wait_event(done)
             rgb_d.record_stream(torch.cuda.current_stream())
             dep_d.record_stream(torch.cuda.current_stream())
-            yield self.pre(rgb_d, dep_d, params)
+            x, y = self.pre(rgb_d, dep_d, params)
+            if self.native_depth:
+                hw = tuple(dep_d.shape[1:])
+                self.view = test_view(hw) if self.ds.split == "test" else val_view(hw, self.ds.resize, self.ds.output_size)
+                y = dep_d.unsqueeze(1)
+            yield x, y

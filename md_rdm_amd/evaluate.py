@@ -19,26 +19,56 @@ resized to the resolution of the depth the loader returns, valid pixels only (fi
 alignment (--align), the aligned prediction clamped to the depth range, and the Eigen et al. error set per image, averaged over the images.
 Its figures are NOT comparable with the reference protocol's: ``rmse`` there is the true root mean square, and the deltas are taken of aligned
 linear depth.  Images without a valid pixel are left out and counted as ``skipped``.  The rows then show input | raw depth | aligned prediction.
-NB the command scores at the LOADER's output size (--size, 226x226 by default: the depth after the split's Resize + CenterCrop), and --crop is in
-that frame's coordinates.  Its figures are therefore not yet the 480x640 Eigen-crop numbers of the published NYU tables; the kernel and
-``harness.evaluate`` take depth of any size, so batches that carry the depth at its native resolution are scored there.
+Without --native the command scores at the LOADER's output size (--size, 226x226 by default: the depth after the split's Resize + CenterCrop), and
+--crop is in that frame's coordinates.
 
+``--native`` (with --protocol standard and --nyu_path) scores against the RAW depth of every sample instead, at its own resolution: the loader hands
+over the depth untouched (``PrefetchLoader(native_depth=True)``) together with the rectangle of that frame which the network input covers (the
+split's ``view``; for --split test, Resize(500) -> CenterCrop((480, 640)) leaves rows 9.6 to 470.4 and columns 12.49 to 627.51 of a 480x640 frame), and
+the kernel resamples the map over that rectangle (``rdm_eval_standard_view_f64``, include/rdm_eval_view.h).  ``--crop eigen`` is the NYU crop of the
+published tables, rows [45, 471) and columns [41, 601) of the 480x640 frame (``--crop garg``: the KITTI crop, fractions of the frame); four integers
+still work.  ``--flip`` averages every map with the mirrored map of the mirrored input, the test-time augmentation of those tables, under either
+protocol (two passes per batch).  ``--split test --protocol standard --native --crop eigen [--flip]`` therefore gives the 480x640 Eigen-crop figures of
+the published NYU tables, with one caveat: a few pixels of the Eigen crop lie outside the view - row 470 of the test transform, whose centre
+470.5 is past the view's last row edge 470.4 - and there the prediction is the map's replicated edge, not something the network saw.
+
+  python -m md_rdm_amd.evaluate --checkpoint last.ckpt --nyu_path /data/nyudepthv2 --split test --protocol standard --native --crop eigen --flip --out results.json
   python -m md_rdm_amd.evaluate --checkpoint last.ckpt --nyu_path /data/nyudepthv2 --split test --protocol standard --crop 8 8 218 218 --out results.json
 """
 import json
 import os
 import sys
-from argparse import ArgumentParser
+from argparse import SUPPRESS, ArgumentParser
 
 # multi-process GPU work on this ROCm stack needs dmabuf IPC (see md_rdm_amd/train.py); must be set before the first HIP call
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 NO_GPU = "md_rdm_amd.evaluate: no GPU is visible to this process (torch.cuda.is_available() is False); evaluation runs on the MI355X only"
+CROP_NAMES = ("eigen", "garg")                                                             # metrics.NAMED_CROPS
 DEFAULT_METRICS = ["delta1", "delta2", "delta3", "mse", "mae", "log10", "rmse"]            # train.py's --metrics default
 
 
+class CropNameParser(ArgumentParser):
+    """--crop takes four integers; ``--crop eigen`` / ``--crop garg`` is read as the option --crop_name, whose value then stands in ``crop``"""
+
+    def parse_known_args(self, args=None, namespace=None):
+        args = list(sys.argv[1:] if args is None else args)
+        for i, a in enumerate(args):
+            if a == "--crop" and i + 1 < len(args) and args[i + 1] in CROP_NAMES:
+                args[i] = "--crop_name"
+            elif a.startswith("--crop=") and a[7:] in CROP_NAMES:
+                args[i] = "--crop_name=" + a[7:]
+        ns, rest = super().parse_known_args(args, namespace)
+        if ns.crop_name is not None:
+            if ns.crop is not None:
+                self.error("argument --crop: given twice, as a name and as four integers")
+            ns.crop = ns.crop_name
+        del ns.crop_name
+        return ns, rest
+
+
 def build_parser():
-    p = ArgumentParser("md_rdm_amd.evaluate", description="Score a checkpoint on the NYU val / test split, on the MI355X-native stack")
+    p = CropNameParser("md_rdm_amd.evaluate", description="Score a checkpoint on the NYU val / test split, on the MI355X-native stack")
     p.add_argument("--checkpoint", type=str, default=None, help="Lightning .ckpt or state_dict; without it the hash-filled model is used (a warning says so)")
     p.add_argument("--nyu_path", type=str, default=None, help="directory of raw NYU samples (.h5 / .npz), as for md_rdm_amd.train")
     p.add_argument("--split", type=str, default="val", choices=["val", "test"])
@@ -55,7 +85,12 @@ def build_parser():
     p.add_argument("--align", type=str, default="median", choices=["none", "median", "logmean"], help="standard protocol: per-image scale alignment")
     p.add_argument("--min_depth", type=float, default=1e-3, help="standard protocol: valid pixels have min_depth < d < max_depth; the prediction is clamped to the range")
     p.add_argument("--max_depth", type=float, default=10.0)
-    p.add_argument("--crop", type=int, nargs=4, default=None, metavar=("Y0", "X0", "Y1", "X1"), help="standard protocol: score rows [Y0, Y1) and columns [X0, X1) only")
+    p.add_argument("--crop", type=int, nargs=4, default=None, metavar=("Y0", "X0", "Y1", "X1"), help="standard protocol: score rows [Y0, Y1) and columns [X0, X1) only; "
+                   "or one name in place of the four integers: eigen (NYU: 45 41 471 601 of the 480x640 frame) or garg (KITTI: fractions of the frame)")
+    p.add_argument("--crop_name", type=str, default=None, choices=list(CROP_NAMES), help=SUPPRESS)
+    p.add_argument("--native", action="store_true", help="standard protocol, --nyu_path: score against every sample's RAW depth at its own resolution, the map "
+                   "placed on the part of that frame which the network input covers")
+    p.add_argument("--flip", action="store_true", help="average every map with the mirrored map of the mirrored input (two passes per batch)")
     p.add_argument("--out", type=str, default=None, help="write the result as JSON here")
     p.add_argument("--worker", default=6, type=int, help="threads that decode raw samples (--nyu_path)")
     p.add_argument("--rows", type=str, default=None, metavar="DIR", help="write input | normalised target | prediction PNG rows here")
@@ -78,13 +113,27 @@ def make_computer(args):
     """the metric computer the flags ask for; every refusal is a SystemExit before anything touches a GPU"""
     from .metrics import MetricComputation, StandardMetrics
     try:
+        if args.native and args.protocol != "standard":
+            raise SystemExit("md_rdm_amd.evaluate: --native needs --protocol standard; the reference protocol scores the normalised 128x128 target")
+        if args.native and not args.nyu_path:
+            raise SystemExit("md_rdm_amd.evaluate: --native needs --nyu_path: it scores the raw depth of the samples, which --synthetic does not have")
+        if args.native and args.rows:
+            raise SystemExit("md_rdm_amd.evaluate: --rows with --native is not built: the input shows the view, the raw depth the whole frame")
+        if isinstance(args.crop, str) and args.protocol != "standard":
+            raise SystemExit("md_rdm_amd.evaluate: --crop %s belongs to --protocol standard; the reference protocol scores the whole 128x128 target" % args.crop)
         if args.protocol == "reference":
             return MetricComputation(args.metrics)
         if args.exp_pred:
             raise SystemExit("md_rdm_amd.evaluate: --exp_pred belongs to --protocol reference; the standard protocol always compares linear depth")
         names = None if list(args.metrics) == DEFAULT_METRICS else args.metrics          # --metrics left alone: the standard list
         H, W = args.size
-        if args.crop is not None and not (0 <= args.crop[0] < args.crop[2] <= H and 0 <= args.crop[1] < args.crop[3] <= W):
+        if isinstance(args.crop, str):
+            if not args.native:                                                           # the depth has the loader's size: the name resolves now
+                StandardMetrics(crop=args.crop).resolve_crop(H, W)
+        elif args.crop is not None and args.native:                                       # the raw size is not known yet: the kernel checks the frame
+            if not (0 <= args.crop[0] < args.crop[2] and 0 <= args.crop[1] < args.crop[3]):
+                raise SystemExit("md_rdm_amd.evaluate: --crop %s is empty" % " ".join(map(str, args.crop)))
+        elif args.crop is not None and not (0 <= args.crop[0] < args.crop[2] <= H and 0 <= args.crop[1] < args.crop[3] <= W):
             raise SystemExit("md_rdm_amd.evaluate: --crop %s is empty or outside the %dx%d frame" % (" ".join(map(str, args.crop)), H, W))
         return StandardMetrics(names, align=args.align, min_depth=args.min_depth, max_depth=args.max_depth, crop=args.crop)
     except KeyError as e:
@@ -132,6 +181,7 @@ def main(argv=None):
         filler.fill_state_dict(model.state_dict())
     model = model.to(dev).eval().set_precision("bf16" if args.precision == 16 else "f32")
     H, W = args.size
+    native = {"view": None, "crop": None}                                # --native: of the last batch this rank scored
 
     if args.synthetic:
         xs, ys = synthetic_samples(args.synthetic, H, W)
@@ -146,13 +196,17 @@ def main(argv=None):
         from .dataloaders import NYUDataset, PrefetchLoader
         ds = NYUDataset(args.nyu_path, split=args.split, output_size=(H, W))
         loader = PrefetchLoader(ds, args.batch_size, shuffle=False, device=dev, drop_last=False, rank=rank, world=world, workers=args.worker,
-                                indices=range(len(ds)))
+                                indices=range(len(ds)), native_depth=args.native)
 
         def batches():
-            return iter(loader)
+            for x, y in loader:
+                if args.native:
+                    computer.view = loader.view                          # this batch's raw frame
+                    native.update(view=list(loader.view), crop=computer.resolve_crop(y.shape[2], y.shape[3]))
+                yield x, y
         source = args.split
     rows = []
-    result = harness.evaluate(model, batches(), computer, exp_pred=args.exp_pred, rows_out=rows if args.rows else None, rows_max=args.rows_max)
+    result = harness.evaluate(model, batches(), computer, exp_pred=args.exp_pred, rows_out=rows if args.rows else None, rows_max=args.rows_max, flip=args.flip)
     if args.rows:
         from . import viz
         os.makedirs(args.rows, exist_ok=True)
@@ -172,8 +226,11 @@ def main(argv=None):
                       "relative_decoders": list(args.relative_decoders), "checkpoint": args.checkpoint, "world": world,
                       "metrics": {name: result[name] for name in computer.names}, "protocol": args.protocol}
             if standard:
-                record.update(align=args.align, min_depth=args.min_depth, max_depth=args.max_depth, crop=list(args.crop) if args.crop else None,
-                              skipped=result["skipped"])
+                crop = native["crop"] if args.native else computer.resolve_crop(H, W)          # a named crop as its integers
+                record.update(align=args.align, min_depth=args.min_depth, max_depth=args.max_depth, crop=list(crop) if crop else None,
+                              skipped=result["skipped"], native=bool(args.native), view=native["view"], flip=bool(args.flip))
+            elif args.flip:
+                record["flip"] = True
             d = os.path.dirname(os.path.abspath(args.out))
             os.makedirs(d, exist_ok=True)
             with open(args.out, "w") as fh:

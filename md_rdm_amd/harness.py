@@ -69,7 +69,7 @@ def validation_step(model, x, y):
     return y_hat, normalize(y)
 
 
-def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_out=None, rows_max=16):
+def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_out=None, rows_max=16, flip=False):
     """Score a model on an iterable of (x, raw depth) batches of ANY batch size: per batch ``model.predict(x)`` and ONE launch from the map and
     the raw depth to a row of metric sums per sample (``MetricComputation.compute_rows``); the rows stay on the device and come over in one
     copy after the last batch.  The result, {metric: mean over the samples of the per-sample value, "n": samples}, is what the reference's
@@ -85,7 +85,9 @@ def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_ou
     alignment, the Eigen et al. error set; include/rdm_eval.h), again ``predict`` + ONE launch per batch with the rows kept on the device.  The
     result is the mean over the samples of the per-sample values (the per-image averaging of the NYU / KITTI protocols); samples without a
     valid pixel are left out of the means and counted in ``"skipped"``; if every sample is skipped it raises.  ``rows_out`` then shows
-    input | raw depth | the aligned, clamped prediction over one colour range.  ``exp_pred`` does not apply."""
+    input | raw depth | the aligned, clamped prediction over one colour range.  ``exp_pred`` does not apply.  A StandardMetrics with a ``view``
+    scores depth of which the network saw a part (``PrefetchLoader(native_depth=True)``: the raw frame and ``loader.view``).
+    ``flip``: every map is ``model.predict(x, flip=True)``, the mirror test-time augmentation of the published tables (two passes per batch)."""
     import torch.distributed as dist
     from .metrics import MetricComputation, StandardMetrics, mean_over_shards
     standard = isinstance(metrics, StandardMetrics)
@@ -94,7 +96,7 @@ def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_ou
     mc = metrics if isinstance(metrics, (MetricComputation, StandardMetrics)) else MetricComputation(list(metrics))
     rows, maps = [], []
     for x, y in batches:
-        pred = model.predict(x)
+        pred = model.predict(x, flip=True) if flip else model.predict(x)
         want = rows_out is not None and len(rows_out) < rows_max
         if standard:
             tgt = torch.empty(y.shape, dtype=torch.float64, device=pred.device) if want else None      # q, at the depth's resolution

@@ -95,6 +95,25 @@ class MetricComputation:
 # the standard protocol (include/rdm_eval.h): name -> how the value is formed from a row of rdm_eval_standard_f64
 _STANDARD = ("delta1", "delta2", "delta3", "abs_rel", "sq_rel", "rmse", "rmse_log", "silog", "log10", "mae", "scale")
 STANDARD_COLS = 16
+EIGEN_CROP = (45, 41, 471, 601)                                       # NYU, of the 480x640 frame: rows [45, 471), columns [41, 601)
+GARG_CROP = (0.40810811, 0.03594771, 0.99189189, 0.96405229)          # KITTI: y0, x0, y1, x1 as fractions of H, W, H, W
+NAMED_CROPS = ("eigen", "garg")
+
+
+def named_crop(name, H, W):
+    """A crop of the published protocols as (y0, x0, y1, x1) of an (H, W) depth frame.  ``"eigen"``: the NYU crop of Eigen et al.,
+    (45, 41, 471, 601), defined for the 480x640 frame only - any other size raises.  ``"garg"``: the KITTI crop of Garg et al., the fractions
+    0.40810811 / 0.99189189 of H and 0.03594771 / 0.96405229 of W; each product is TRUNCATED to an integer (``int()``, as the usual evaluation
+    scripts' ``astype(int32)`` does; the products are positive, so this is the floor): 352x1216 -> (143, 43, 349, 1172)."""
+    if name == "eigen":
+        if (H, W) != (480, 640):
+            raise ValueError(f"crop 'eigen' is the NYU crop of the 480x640 frame; the depth is {H}x{W}")
+        return EIGEN_CROP
+    if name == "garg":
+        f = GARG_CROP
+        return (int(f[0] * H), int(f[1] * W), int(f[2] * H), int(f[3] * W))
+    raise ValueError(f"crop '{name}' is not one of {NAMED_CROPS}")
+
 
 
 class StandardMetrics:
@@ -110,11 +129,15 @@ class StandardMetrics:
 
     NB ``rmse`` here is the TRUE root mean square.  It is not the reference's metric of the same name (``MetricComputation``'s 'rmse' is the
     reference's mean sqrt((p-t)^2/t), metrics.py:107-110), and none of these figures is comparable with the reference protocol's.
-    ``compute_rows`` is one launch per batch (``rdm_eval_standard_f64``); ``values_from_rows`` forms the values on the host."""
+    ``compute_rows`` is one launch per batch (``rdm_eval_standard_f64``); ``values_from_rows`` forms the values on the host.
+    ``crop`` may also name a published crop, ``"eigen"`` (NYU) or ``"garg"`` (KITTI): it resolves when the depth's shape is known (``named_crop``).
+    ``view`` = (vy0, vx0, vh, vw): the rectangle of the depth frame, in depth pixels, that the predicted map covers (include/rdm_eval_view.h;
+    ``dataloaders.nyu.test_view`` for raw NYU depth); None: the map covers the whole frame.  Depth pixels outside the view are scored against
+    the map's replicated edge.  The attribute may be set between batches."""
 
     available = _STANDARD
 
-    def __init__(self, names=None, align="median", min_depth=1e-3, max_depth=10.0, crop=None):
+    def __init__(self, names=None, align="median", min_depth=1e-3, max_depth=10.0, crop=None, view=None):
         names = list(_STANDARD) if names is None else list(names)
         for m in names:
             if m not in _STANDARD:
@@ -123,16 +146,38 @@ class StandardMetrics:
             raise ValueError(f"align '{align}' is not one of {sorted(_lib.EVAL_ALIGN)}")
         if not (0 <= float(min_depth) < float(max_depth)):
             raise ValueError(f"need 0 <= min_depth < max_depth, got {min_depth}, {max_depth}")
-        if crop is not None:
+        if isinstance(crop, str):
+            if crop not in NAMED_CROPS:
+                raise ValueError(f"crop '{crop}' is not one of {NAMED_CROPS}")
+        elif crop is not None:
             crop = tuple(int(c) for c in crop)
             if len(crop) != 4 or not (0 <= crop[0] < crop[2] and 0 <= crop[1] < crop[3]):
                 raise ValueError(f"crop must be (y0, x0, y1, x1) with 0 <= y0 < y1 and 0 <= x0 < x1, got {crop}")
         self.names, self.align, self.min_depth, self.max_depth, self.crop = names, align, float(min_depth), float(max_depth), crop
+        self.view = view
+
+    @property
+    def view(self):
+        return self._view
+
+    @view.setter
+    def view(self, view):
+        import math
+        if view is not None:
+            view = tuple(float(v) for v in view)
+            if len(view) != 4 or not all(math.isfinite(v) for v in view) or not (view[2] > 0 and view[3] > 0):
+                raise ValueError(f"view must be (vy0, vx0, vh, vw), finite with vh > 0 and vw > 0, got {view}")
+        self._view = view
+
+    def resolve_crop(self, H, W):
+        """the crop of an (H, W) depth frame as (y0, x0, y1, x1), or None: a named crop becomes its integers here"""
+        return named_crop(self.crop, H, W) if isinstance(self.crop, str) else self.crop
 
     def compute_rows(self, pred, depth, pred_out=None):
         """The (B,1,128,128) float64 log map ``predict`` returns and the loader's raw (B,1,H,W) float32 / float64 depth -> the (B,16) float64
         DEVICE tensor of per-sample sums (columns: include/rdm_eval.h).  One launch, nothing is copied to the host and nothing synchronises.
-        ``pred_out`` (B,1,H,W) float64: optionally receives the aligned, clamped prediction at every pixel."""
+        ``pred_out`` (B,1,H,W) float64: optionally receives the aligned, clamped prediction at every pixel.
+        With a ``view`` the launch is ``rdm_eval_standard_view_f64``, without one ``rdm_eval_standard_f64``."""
         import ctypes as C
         if not pred.is_cuda or not depth.is_cuda:
             raise _lib.RdmError("metrics run on the GPU only")
@@ -148,9 +193,15 @@ class StandardMetrics:
         need = L.rdm_eval_standard_workspace_bytes(B, H, W)
         ws = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=p.device)
         rows = torch.empty(B, STANDARD_COLS, dtype=torch.float64, device=p.device)
-        crop = (C.c_int32 * 4)(*self.crop) if self.crop is not None else None
-        _lib.check(L.rdm_eval_standard_f64(_lib.ptr(p), _lib.ptr(d), int(d.dtype == torch.float64), B, H, W, _lib.EVAL_ALIGN[self.align], self.min_depth,
-                                           self.max_depth, crop, _lib.ptr(rows), _lib.ptr(pred_out), _lib.ptr(ws), ws.numel() * 8, _lib.stream()))
+        crop = self.resolve_crop(H, W)
+        crop = (C.c_int32 * 4)(*crop) if crop is not None else None
+        if self.view is not None:
+            _lib.check(L.rdm_eval_standard_view_f64(_lib.ptr(p), _lib.ptr(d), int(d.dtype == torch.float64), B, H, W, _lib.EVAL_ALIGN[self.align], self.min_depth,
+                                                    self.max_depth, crop, (C.c_double * 4)(*self.view), _lib.ptr(rows), _lib.ptr(pred_out), _lib.ptr(ws),
+                                                    ws.numel() * 8, _lib.stream()))
+        else:
+            _lib.check(L.rdm_eval_standard_f64(_lib.ptr(p), _lib.ptr(d), int(d.dtype == torch.float64), B, H, W, _lib.EVAL_ALIGN[self.align], self.min_depth,
+                                               self.max_depth, crop, _lib.ptr(rows), _lib.ptr(pred_out), _lib.ptr(ws), ws.numel() * 8, _lib.stream()))
         return rows
 
     def values_from_rows(self, rows):

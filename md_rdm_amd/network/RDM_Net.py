@@ -373,6 +373,12 @@ class _ConvStackFunction(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
+def mirror_average(predict, x):
+    """Mirror test-time augmentation of a map predictor: the mean of the map of ``x`` and the mirrored map of the mirrored ``x``, two calls of
+    ``predict`` on batches of ``x``'s size, the unmirrored one first.  ``DepthEstimationNet.predict(x, flip=True)`` is this of its own maps."""
+    return 0.5 * (predict(x) + predict(x.flip(-1)).flip(-1))
+
+
 class DepthEstimationNet(BaseModel):
     """Drop-in for the reference class (RDM_Net.py:25-135)."""
 
@@ -718,18 +724,34 @@ class DepthEstimationNet(BaseModel):
             return None
         return n
 
-    def predict(self, x, linear=False, size=None, return_counts=False):
+    def predict(self, x, linear=False, size=None, return_counts=False, flip=False):
         """The (B,1,128,128) float64 map of log relative depth for a batch of images - what the reference computes for an image,
         ``recombination(model(x)[0])`` (optimize_components returns its predictions unchanged, computations.py:499-510) - without a target.
         Eval mode only; the forward runs at the model's ``precision``.  The ordinal-only model with a square power-of-two head (226/228-pixel
         inputs) takes the d_1 logits to the map in ONE launch (rdm_predict_tail_f32); models with relative decoders and rectangular heads
         compose the single operators exactly as ``forward`` + ``recombination`` do.
         ``linear``: return float32 ``exp`` of the map instead.  ``size=(H, W)``: bicubic ``resize`` of the log map first.
-        ``return_counts``: also return the (B,1,h,w) int64 DORN count map (``forward``'s second result)."""
+        ``return_counts``: also return the (B,1,h,w) int64 DORN count map (``forward``'s second result).
+        ``flip``: mirror test-time augmentation, by definition ``0.5 * (predict(x) + predict(x.flip(-1)).flip(-1))`` of the log-domain maps:
+        two passes at the caller's batch size, averaged before ``size`` and ``linear`` apply.  The counts are the unmirrored pass's."""
         if self.training:
             raise _lib.RdmError("predict is inference only (eval-mode BatchNorm): call model.eval() first")
         if not x.is_cuda:
             raise _lib.RdmError("DepthEstimationNet runs on the MI355X only (input is on %s); there is no CPU fallback" % x.device)
+        if flip:
+            with torch.no_grad():
+                passes = []
+
+                def plain(v):
+                    passes.append(self.predict(v, return_counts=return_counts))
+                    return passes[-1][0] if return_counts else passes[-1]
+                out = mirror_average(plain, x)
+                counts = passes[0][1] if return_counts else None
+                if size is not None:
+                    out = cp.resize(out, tuple(size))
+                if linear:
+                    out = torch.exp(out).float()
+                return (out, counts) if return_counts else out
         with torch.no_grad():
             B, _, H, W = x.shape
             _, _, oh, ow = self._plan(B, H, W)

@@ -11,6 +11,7 @@ network inputs (filler.synthetic_batch) of --size instead.  One ``.npy`` per inp
 float32 ``exp`` of it with --linear, resized to the frame region the network saw ((480, 640), or --size for synthetic inputs) with --full_res.
 ``--png`` writes ``NAME.png`` beside each ``.npy``: the saved map in jet colours (md_rdm_amd.viz, one launch per batch), over its own range or
 over ``--png_range LO HI`` (comparable frames); ``--png_with_input`` puts the network input to its left, the map resized to the input's size.
+``--flip`` averages every log map with the mirrored map of the mirrored input (``predict(x, flip=True)``: two passes per batch).
 """
 import os
 import sys
@@ -30,6 +31,8 @@ def build_parser():
     p.add_argument("--out", type=str, required=True, help="directory for the .npy maps")
     p.add_argument("--linear", action="store_true", help="write float32 exp(map) instead of the float64 log map")
     p.add_argument("--full_res", action="store_true", help="bicubic resize of the log map to the frame region the network saw (480x640; --size for --synthetic)")
+    p.add_argument("--flip", action="store_true", help="average every map with the mirrored map of the mirrored input (log domain, before --linear and --full_res; "
+                   "two passes per batch)")
     p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N hash-generated inputs (filler.synthetic_batch) instead of files")
     p.add_argument("--relative_decoders", type=int, nargs="*", default=[], help="subset of 6 7 8 9 10, as in md_rdm_amd.train")
     p.add_argument("--png", action="store_true", help="also write NAME.png: the saved map in jet colours (honours --linear and --full_res)")
@@ -122,7 +125,7 @@ def main(argv=None):
                 raise SystemExit("md_rdm_amd.predict: %s (%dx%d frame): %s" % (items[i][0], H, W, e))
             x, _ = pre(rgb, dummy, params)
             region = (480, 640)
-        maps = model.predict(x, linear=args.linear, size=region if args.full_res else None)
+        maps = model.predict(x, linear=args.linear, size=region if args.full_res else None, flip=args.flip)
         out = maps.cpu().numpy()
         dt = time.perf_counter() - t0
         if args.png:
