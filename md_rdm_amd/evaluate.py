@@ -32,7 +32,12 @@ protocol (two passes per batch).  ``--split test --protocol standard --native --
 the published NYU tables, with one caveat: a few pixels of the Eigen crop lie outside the view - row 470 of the test transform, whose centre
 470.5 is past the view's last row edge 470.4 - and there the prediction is the map's replicated edge, not something the network saw.
 
+``--scale sid`` (standard protocol) adds the metric scale of the d_1 DORN head to every log map before it is scored: the mean log depth of the head's
+labels under the ``--sid`` parameter set, ``--sid_offset`` into each bin (``depth.sid_log_scale``).  With ``--align none`` the figures are then those
+of METRIC predictions, in the depth's unit.
+
   python -m md_rdm_amd.evaluate --checkpoint last.ckpt --nyu_path /data/nyudepthv2 --split test --protocol standard --native --crop eigen --flip --out results.json
+  python -m md_rdm_amd.evaluate --checkpoint last.ckpt --nyu_path /data/nyudepthv2 --split test --protocol standard --native --align none --scale sid --out results.json
   python -m md_rdm_amd.evaluate --checkpoint last.ckpt --nyu_path /data/nyudepthv2 --split test --protocol standard --crop 8 8 218 218 --out results.json
 """
 import json
@@ -91,6 +96,9 @@ def build_parser():
     p.add_argument("--native", action="store_true", help="standard protocol, --nyu_path: score against every sample's RAW depth at its own resolution, the map "
                    "placed on the part of that frame which the network input covers")
     p.add_argument("--flip", action="store_true", help="average every map with the mirrored map of the mirrored input (two passes per batch)")
+    p.add_argument("--scale", type=str, default=None, choices=["sid"], help="standard protocol: add the DORN head's metric log scale to every map (with --align none: metric scores)")
+    p.add_argument("--sid", type=str, default=None, metavar="NAME", help="--scale sid: the head's SID parameter set: nyu (default), kitti, floorplan3d, Structured3D")
+    p.add_argument("--sid_offset", type=float, default=None, metavar="F", help="--scale sid: position inside a label's bin, 0 (default) = lower edge, 0.5 = centre")
     p.add_argument("--out", type=str, default=None, help="write the result as JSON here")
     p.add_argument("--worker", default=6, type=int, help="threads that decode raw samples (--nyu_path)")
     p.add_argument("--rows", type=str, default=None, metavar="DIR", help="write input | normalised target | prediction PNG rows here")
@@ -119,6 +127,14 @@ def make_computer(args):
             raise SystemExit("md_rdm_amd.evaluate: --native needs --nyu_path: it scores the raw depth of the samples, which --synthetic does not have")
         if args.native and args.rows:
             raise SystemExit("md_rdm_amd.evaluate: --rows with --native is not built: the input shows the view, the raw depth the whole frame")
+        if args.scale is not None and args.protocol != "standard":
+            raise SystemExit("md_rdm_amd.evaluate: --scale %s needs --protocol standard; the reference protocol compares maps normalised by their geometric mean" % args.scale)
+        if (args.sid is not None or args.sid_offset is not None) and args.scale is None:
+            raise SystemExit("md_rdm_amd.evaluate: --sid and --sid_offset need --scale sid")
+        if args.sid is not None:
+            from .depth import SID
+            if args.sid not in SID:
+                raise SystemExit("md_rdm_amd.evaluate: --sid %s is not one of %s" % (args.sid, ", ".join(SID)))
         if isinstance(args.crop, str) and args.protocol != "standard":
             raise SystemExit("md_rdm_amd.evaluate: --crop %s belongs to --protocol standard; the reference protocol scores the whole 128x128 target" % args.crop)
         if args.protocol == "reference":
@@ -206,7 +222,8 @@ def main(argv=None):
                 yield x, y
         source = args.split
     rows = []
-    result = harness.evaluate(model, batches(), computer, exp_pred=args.exp_pred, rows_out=rows if args.rows else None, rows_max=args.rows_max, flip=args.flip)
+    result = harness.evaluate(model, batches(), computer, exp_pred=args.exp_pred, rows_out=rows if args.rows else None, rows_max=args.rows_max, flip=args.flip,
+                              **(dict(scale=args.scale, sid=args.sid or "nyu", sid_offset=args.sid_offset or 0.0) if args.scale else {}))
     if args.rows:
         from . import viz
         os.makedirs(args.rows, exist_ok=True)
@@ -229,6 +246,8 @@ def main(argv=None):
                 crop = native["crop"] if args.native else computer.resolve_crop(H, W)          # a named crop as its integers
                 record.update(align=args.align, min_depth=args.min_depth, max_depth=args.max_depth, crop=list(crop) if crop else None,
                               skipped=result["skipped"], native=bool(args.native), view=native["view"], flip=bool(args.flip))
+                if args.scale:
+                    record.update(scale=args.scale, sid=args.sid or "nyu", sid_offset=args.sid_offset or 0.0)
             elif args.flip:
                 record["flip"] = True
             d = os.path.dirname(os.path.abspath(args.out))

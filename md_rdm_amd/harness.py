@@ -69,7 +69,7 @@ def validation_step(model, x, y):
     return y_hat, normalize(y)
 
 
-def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_out=None, rows_max=16, flip=False):
+def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_out=None, rows_max=16, flip=False, scale=None, sid="nyu", sid_offset=0.0):
     """Score a model on an iterable of (x, raw depth) batches of ANY batch size: per batch ``model.predict(x)`` and ONE launch from the map and
     the raw depth to a row of metric sums per sample (``MetricComputation.compute_rows``); the rows stay on the device and come over in one
     copy after the last batch.  The result, {metric: mean over the samples of the per-sample value, "n": samples}, is what the reference's
@@ -87,16 +87,28 @@ def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_ou
     valid pixel are left out of the means and counted in ``"skipped"``; if every sample is skipped it raises.  ``rows_out`` then shows
     input | raw depth | the aligned, clamped prediction over one colour range.  ``exp_pred`` does not apply.  A StandardMetrics with a ``view``
     scores depth of which the network saw a part (``PrefetchLoader(native_depth=True)``: the raw frame and ``loader.view``).
-    ``flip``: every map is ``model.predict(x, flip=True)``, the mirror test-time augmentation of the published tables (two passes per batch)."""
+    ``flip``: every map is ``model.predict(x, flip=True)``, the mirror test-time augmentation of the published tables (two passes per batch).
+    ``scale="sid"`` (standard protocol only; the reference protocol compares normalised maps): ``predict`` also hands over the DORN counts, and
+    ``depth.sid_log_scale(counts, sid, sid_offset)`` is added to every log map before the metrics launch, so ``StandardMetrics(align="none")``
+    scores metric predictions; ``return_maps`` then returns the shifted maps.  None leaves every path as it was."""
     import torch.distributed as dist
     from .metrics import MetricComputation, StandardMetrics, mean_over_shards
     standard = isinstance(metrics, StandardMetrics)
     if standard and exp_pred:
         raise ValueError("evaluate: exp_pred belongs to the reference protocol; the standard protocol always compares linear depth")
+    if scale not in (None, "sid"):
+        raise ValueError("evaluate: scale must be None or 'sid', got %r" % (scale,))
+    if scale is not None and not standard:
+        raise ValueError("evaluate: scale='sid' belongs to the standard protocol; the reference protocol compares maps normalised by their geometric mean")
     mc = metrics if isinstance(metrics, (MetricComputation, StandardMetrics)) else MetricComputation(list(metrics))
     rows, maps = [], []
     for x, y in batches:
-        pred = model.predict(x, flip=True) if flip else model.predict(x)
+        if scale is not None:
+            from . import depth
+            pred, counts = model.predict(x, return_counts=True, flip=flip)
+            pred = pred + depth.sid_log_scale(counts, sid, sid_offset).reshape(-1, 1, 1, 1)
+        else:
+            pred = model.predict(x, flip=True) if flip else model.predict(x)
         want = rows_out is not None and len(rows_out) < rows_max
         if standard:
             tgt = torch.empty(y.shape, dtype=torch.float64, device=pred.device) if want else None      # q, at the depth's resolution

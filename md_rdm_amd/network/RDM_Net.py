@@ -775,6 +775,14 @@ class DepthEstimationNet(BaseModel):
                 out = lin if lin is not None else torch.exp(out).float()
             return (out, counts) if return_counts else out
 
+    def predict_metric(self, x, frame_hw, view=None, flip=False, **kwargs):
+        """Metric depth frames for a batch of images: ``predict(x, return_counts=True, flip=flip)`` followed by ``depth.metric_frames`` of the
+        map and the DORN counts (under ``flip`` the unmirrored pass's) over the (h, w) frame, of which the network saw ``view``.  ``kwargs`` are
+        ``metric_frames``' (log_scale, sid, offset, unit, outside, want); the result is its dict."""
+        from .. import depth
+        log_map, counts = self.predict(x, return_counts=True, flip=flip)
+        return depth.metric_frames(log_map, frame_hw, view=view, counts=counts, **kwargs)
+
     # ---- the reference forward (RDM_Net.py:70-135) -----------------------------------------
     def forward(self, x):
         bf16 = self.precision == "bf16"

@@ -12,6 +12,15 @@ float32 ``exp`` of it with --linear, resized to the frame region the network saw
 ``--png`` writes ``NAME.png`` beside each ``.npy``: the saved map in jet colours (md_rdm_amd.viz, one launch per batch), over its own range or
 over ``--png_range LO HI`` (comparable frames); ``--png_with_input`` puts the network input to its left, the map resized to the input's size.
 ``--flip`` averages every log map with the mirrored map of the mirrored input (``predict(x, flip=True)``: two passes per batch).
+
+``--metric`` writes depth in metres instead (md_rdm_amd.depth, one launch per batch): the scale is the mean log depth of the d_1 DORN head's
+labels under the ``--sid`` parameter set (``--sid_offset 0.5``: bin centres instead of lower bin edges), and the ``.npy`` is the float32
+(1,h,w) frame - 128x128, the --full_res region, or with ``--native`` the input frame's own shape, the map placed on the rectangle of it the
+network saw (``nyu.test_view``; the pixels outside are 0, "no measurement", or with ``--outside edge`` the map's replicated edge).
+``--png16`` also writes ``NAME_depth.png``, the 16-bit greyscale depth PNG downstream tools read, in steps of ``--depth_unit`` metres
+(default 0.001: millimetres; 65535 saturates).  ``--png`` then colours the saved metric map.
+
+  python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --png16 frame0.npy
 """
 import os
 import sys
@@ -38,6 +47,13 @@ def build_parser():
     p.add_argument("--png", action="store_true", help="also write NAME.png: the saved map in jet colours (honours --linear and --full_res)")
     p.add_argument("--png_range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="fixed colour range instead of each map's own minimum / maximum")
     p.add_argument("--png_with_input", action="store_true", help="the .png shows input | map, the map resized to the network input's size")
+    p.add_argument("--metric", action="store_true", help="write float32 depth in metres, the scale taken from the ordinal (DORN) head")
+    p.add_argument("--sid", type=str, default=None, metavar="NAME", help="--metric: the head's SID parameter set: nyu (default), kitti, floorplan3d, Structured3D")
+    p.add_argument("--sid_offset", type=float, default=None, metavar="F", help="--metric: position inside a label's bin, 0 (default) = lower edge, 0.5 = centre")
+    p.add_argument("--native", action="store_true", help="--metric, file inputs: the output has the input frame's own shape, the map placed on the part the network saw")
+    p.add_argument("--outside", type=str, default=None, choices=["zero", "edge"], help="--metric: pixels outside the view are 0 (default) or the map's replicated edge")
+    p.add_argument("--png16", action="store_true", help="--metric: also write NAME_depth.png, 16-bit greyscale in steps of --depth_unit")
+    p.add_argument("--depth_unit", type=float, default=None, metavar="M", help="--metric: metres per step of the 16-bit PNG (default 0.001)")
     return p
 
 
@@ -47,6 +63,25 @@ def check_png_args(args):
         raise SystemExit("md_rdm_amd.predict: --png_range and --png_with_input need --png")
     if args.png_range is not None and not args.png_range[0] < args.png_range[1]:
         raise SystemExit("md_rdm_amd.predict: --png_range needs LO < HI (got %r %r)" % tuple(args.png_range))
+
+
+def check_metric_args(args):
+    """the metric flags' own rules; raises SystemExit"""
+    if not args.metric:
+        given = [f for f, v in (("--png16", args.png16), ("--sid", args.sid is not None), ("--sid_offset", args.sid_offset is not None),
+                                ("--outside", args.outside is not None), ("--depth_unit", args.depth_unit is not None), ("--native", args.native)) if v]
+        if given:
+            raise SystemExit("md_rdm_amd.predict: --png16, --sid, --sid_offset, --outside, --depth_unit and --native need --metric (got %s)" % " ".join(given))
+        return
+    if args.native and (args.full_res or args.synthetic):
+        raise SystemExit("md_rdm_amd.predict: --native excludes --full_res and --synthetic: it places the map on the raw frame of a file input")
+    if args.linear:
+        raise SystemExit("md_rdm_amd.predict: --metric excludes --linear: the metric map is linear depth already")
+    from .depth import SID
+    if args.sid is not None and args.sid not in SID:
+        raise SystemExit("md_rdm_amd.predict: --sid %s is not one of %s" % (args.sid, ", ".join(SID)))
+    if args.depth_unit is not None and not 0 < args.depth_unit < float("inf"):
+        raise SystemExit("md_rdm_amd.predict: --depth_unit must be positive and finite (got %r)" % args.depth_unit)
 
 
 def load_frame(path):
@@ -77,6 +112,7 @@ def main(argv=None):
     if args.batch_size < 1:
         raise SystemExit("md_rdm_amd.predict: --batch_size must be positive")
     check_png_args(args)
+    check_metric_args(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -125,7 +161,15 @@ def main(argv=None):
                 raise SystemExit("md_rdm_amd.predict: %s (%dx%d frame): %s" % (items[i][0], H, W, e))
             x, _ = pre(rgb, dummy, params)
             region = (480, 640)
-        maps = model.predict(x, linear=args.linear, size=region if args.full_res else None, flip=args.flip)
+        if args.metric:
+            frame = batch.shape[1:3] if args.native else region if args.full_res else (128, 128)
+            planes = model.predict_metric(x, frame, view=nyu.test_view(frame) if args.native else None, flip=args.flip, sid=args.sid or "nyu",
+                                          offset=args.sid_offset or 0.0, unit=args.depth_unit or 1e-3, outside=args.outside or "zero",
+                                          want=("f32", "u16") if args.png16 else ("f32",))
+            maps = planes["f32"].unsqueeze(1)
+            steps = planes["u16"].cpu().numpy() if args.png16 else None
+        else:
+            maps = model.predict(x, linear=args.linear, size=region if args.full_res else None, flip=args.flip)
         out = maps.cpu().numpy()
         dt = time.perf_counter() - t0
         if args.png:
@@ -138,6 +182,8 @@ def main(argv=None):
             np.save(stem + ".npy", m)
             if args.png:
                 viz.write_png(stem + ".png", pngs[n])
+            if args.metric and args.png16:
+                viz.write_png16(stem + "_depth.png", steps[n])
         print("batch of %d: %.1f images/s" % (j - i, (j - i) / dt), flush=True)
         i = j
     return 0

@@ -1,7 +1,30 @@
-"""The one function of the reference's ``utils.py`` that is on the hot path."""
+"""The reference's ``utils.py`` on this stack: ``depth2label_sid``, the one function on the hot path, and the SID tables ``get_depth_sid`` /
+``get_labels_sid`` in the reference's float32 torch arithmetic (the metric-frame kernel uses the float64 formula of include/rdm_depth.h, not these)."""
 import torch
 
 from . import _lib
+
+
+def _sid_tensors(name, cuda):
+    from .depth import SID
+    if name not in SID:
+        raise _lib.RdmError("No Dataset named as %r (one of %s)" % (name, ", ".join(SID)))
+    alpha, beta, K = (torch.tensor(v) for v in SID[name])                  # float32 scalars, as the reference builds them
+    return (alpha.cuda(), beta.cuda(), K.cuda()) if cuda else (alpha, beta, K)
+
+
+def get_depth_sid(args, labels, cuda=False):
+    """utils.py:120-156: metres of SID label(s) under the parameter set named ``args`` ("nyu", "kitti", "floorplan3d", "Structured3D"),
+    alpha * (beta / alpha) ** (label / K) through exp and log in float32; returns float32."""
+    alpha, beta, K = _sid_tensors(args, cuda)
+    return torch.exp(torch.log(alpha) + torch.log(beta / alpha) * labels / K).float()
+
+
+def get_labels_sid(args, depth, cuda=False):
+    """utils.py:159-193: the SID label of metric depth, K * log(depth / alpha) / log(beta / alpha) truncated by ``.int()``; returns int32."""
+    alpha, beta, K = _sid_tensors(args, cuda)
+    labels = K * torch.log(depth / alpha) / torch.log(beta / alpha)
+    return (labels.cuda() if cuda else labels).int()
 
 
 # Label of a NON-POSITIVE depth (log -> NaN -> `.int()`), which the reference leaves to the device it runs on: "cpu" = 0x80000000 (x86; what the

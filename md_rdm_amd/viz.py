@@ -2,8 +2,9 @@
 
 ``colorize`` and ``comparison_rows`` render on the device in ONE launch per batch (``rdm_viz_rows_u8``, include/rdm_viz.h): bicubic resize to the
 output size, the colour range, matplotlib's jet table and the packing to uint8 RGB happen inside, and the result is byte for byte what the
-reference's functions give after ``astype('uint8')``.  ``write_png`` is the one write path: 8-bit RGB with the standard library only (Pillow is
-optional in this project and may be absent where the product runs).
+reference's functions give after ``astype('uint8')``.  ``write_png`` is the one write path for pictures: 8-bit RGB with the standard library only
+(Pillow is optional in this project and may be absent where the product runs); ``write_png16`` beside it writes a 16-bit greyscale plane, the
+format of metric depth maps (md_rdm_amd.depth).
 """
 import struct
 import zlib
@@ -80,5 +81,21 @@ def write_png(path, array):
     raw = np.zeros((h, 1 + 3 * w), dtype=np.uint8)                    # filter byte 0 + the line
     raw[:, 1:] = a.reshape(h, 3 * w)
     data = b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + _chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _chunk(b"IEND", b"")
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
+def write_png16(path, array):
+    """(H,W) uint16 (numpy array or tensor, host or device) -> 16-bit greyscale PNG (colour type 0, big-endian samples), every scan line with
+    filter 0: the interchange format of depth maps (``depth.metric_frames``' "u16" plane: steps of ``unit`` metres, 0 = no measurement).
+    Standard library only."""
+    import numpy as np
+    a = array.detach().cpu().numpy() if isinstance(array, torch.Tensor) else np.asarray(array)
+    if a.ndim != 2 or a.dtype != np.uint16 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("write_png16: need a uint16 (H,W) array, got %s %s" % (a.dtype, a.shape))
+    h, w = a.shape
+    raw = np.zeros((h, 1 + 2 * w), dtype=np.uint8)                    # filter byte 0 + the line
+    raw[:, 1:] = a.astype(">u2").view(np.uint8).reshape(h, 2 * w)
+    data = b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 16, 0, 0, 0, 0)) + _chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _chunk(b"IEND", b"")
     with open(path, "wb") as fh:
         fh.write(data)
