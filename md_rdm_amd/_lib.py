@@ -195,6 +195,12 @@ _OPTIM_SIGNATURES = {
 }
 GRAD_ACC_COPY, GRAD_ACC_ADD, CLIP_MAX_SLOTS = 0, 1, 8        # RDM_GRAD_ACC_*, RDM_CLIP_MAX_SLOTS (include/rdm_optim.h)
 
+# include/rdm_ema.h: the AdamW step that also advances a weight average, and the in-place exchange of two buffers, part of librdm_hip.so, declared in a header of its own
+_EMA_SIGNATURES = {
+    "rdm_adamw_fused_ema": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, i32, f32, vp, f32, vp]),
+    "rdm_ema_swap_f32": (C.c_int, [vp, vp, i64, vp]),
+}
+
 # include/rdm_depth.h: metric depth frames (SID scale, view-mapped resample, float32 and 16-bit planes), part of librdm_hip.so, declared in a header of its own
 _DEPTH_SIGNATURES = {
     "rdm_depth_frames": (C.c_int, [vp, vp, i32, vp, C.POINTER(f64), i32, i32, i32, C.POINTER(f64), i32, f64, vp, vp, vp, i32, vp]),
@@ -222,7 +228,7 @@ def lib():
             raise RdmError(f"{LIB_PATH} not found - run `python -m md_rdm_amd.build` (hipcc --offload-arch=gfx950). "
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _DEPTH_SIGNATURES):
+        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _EMA_SIGNATURES, _DEPTH_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -279,6 +285,10 @@ def eval_view_symbols():
 
 def optim_symbols():
     return list(_OPTIM_SIGNATURES)
+
+
+def ema_symbols():
+    return list(_EMA_SIGNATURES)
 
 
 def depth_symbols():

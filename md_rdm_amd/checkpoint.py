@@ -22,12 +22,21 @@ import torch
 PREFIX = "model."
 
 
+class NoAveragedWeights(KeyError):
+    """from_lightning(ema=True) on a checkpoint without a ``state_dict_ema`` entry."""
+
+
 def to_lightning(model, extra=None, optimizer=None, scheduler=None):
-    """{'state_dict': {'model.<key>': tensor}, ...} as a Lightning 1.1.x .ckpt would hold it (+ our optimiser / scheduler state)."""
+    """{'state_dict': {'model.<key>': tensor}, ...} as a Lightning 1.1.x .ckpt would hold it (+ our optimiser / scheduler state).
+    An optimiser that keeps a weight average (``FusedAdamW(ema_decay=...)``) also gives ``state_dict_ema``: the model's state_dict taken
+    inside ``optimizer.ema_weights()``, under the same keys, so that a reader needs neither the flat layout nor the optimiser."""
     sd = {PREFIX + k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     ckpt = {"state_dict": sd, "pytorch-lightning_version": "1.1.7", "epoch": 0, "global_step": 0}
     if optimizer is not None:
         ckpt["optimizer_states"] = [optimizer.state_dict()]
+        if getattr(optimizer, "ema_decay", None) is not None:
+            with optimizer.ema_weights():
+                ckpt["state_dict_ema"] = {PREFIX + k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     if scheduler is not None:
         ckpt["lr_schedulers"] = [scheduler.state_dict()]
     ckpt.update(extra or {})
@@ -134,12 +143,19 @@ def load_checkpoint_file(path):
         return torch.load(path, map_location="cpu", weights_only=False, pickle_module=_TensorOnlyPickle)
 
 
-def from_lightning(model, ckpt, strict=True, optimizer=None, scheduler=None):
+def from_lightning(model, ckpt, strict=True, optimizer=None, scheduler=None, ema=False):
     """Load a Lightning checkpoint (dict or path) or a bare state_dict into a DepthEstimationNet; returns (load result, ckpt dict).
-    ``optimizer`` / ``scheduler``: restored too when the checkpoint carries OUR training state (see module docstring)."""
+    ``optimizer`` / ``scheduler``: restored too when the checkpoint carries OUR training state (see module docstring).
+    ``ema``: load the averaged weights (``state_dict_ema``, written by a run with ``--ema_decay``) instead; a checkpoint without them raises."""
+    name = "checkpoint %r" % (ckpt,) if isinstance(ckpt, (str, bytes)) else "the checkpoint dict"
     if isinstance(ckpt, (str, bytes)):
         ckpt = load_checkpoint_file(ckpt)
-    sd = ckpt.get("state_dict", ckpt)
+    if ema:
+        if "state_dict_ema" not in ckpt:
+            raise NoAveragedWeights(f"{name} holds no averaged weights (no 'state_dict_ema' entry): it was not written by a run with --ema_decay")
+        sd = ckpt["state_dict_ema"]
+    else:
+        sd = ckpt.get("state_dict", ckpt)
     if any(k.startswith(PREFIX) for k in sd):
         sd = {k[len(PREFIX):]: v for k, v in sd.items() if k.startswith(PREFIX)}
     res = model.load_state_dict(sd, strict=strict)

@@ -1,5 +1,5 @@
-// THE AdamW update body (torch.optim.AdamW, decoupled weight decay, no amsgrad; network/module.py:41), shared by k_adamw (elementwise.hip) and
-// k_adamw_clip (optim.hip) so that the clipped step differs from the plain one in the value of `gscale` alone and agrees with it bit for bit
+// THE AdamW update body (torch.optim.AdamW, decoupled weight decay, no amsgrad; network/module.py:41), shared by k_adamw (elementwise.hip),
+// k_adamw_clip and k_adamw_ema (optim.hip) so that the clipped step differs from the plain one in the value of `gscale` alone and agrees with it bit for bit
 // when that value is the same.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -38,6 +38,39 @@ __device__ __forceinline__ void adamw_sweep(float* p, const float* g, float* m, 
     v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
     w -= (lr / bc1) * (m[i] / (sqrtf(v[i]) * rsqrt_bc2 + eps));
     p[i] = w;
+  }
+}
+
+// the weight average's update from the weight the step has just formed: e + omd (w - e) with omd = 1 - decay rounded once on the host.
+// omd == 0 (decay 1) hands e back as it is, so that -0 and NaN payloads survive too
+__device__ __forceinline__ float ema_elem(float e, float w, float omd) { return omd == 0.f ? e : e + omd * (w - e); }
+
+// adamw_sweep with the average e advanced in the same pass (k_adamw_ema, optim.hip): the quad loop shares adamw_elem, and the tail repeats
+// adamw_sweep's text word for word so that p, m and v get the bytes adamw_sweep gives them; e costs one more 128-bit load and store per quad
+__device__ __forceinline__ void adamw_sweep_ema(float* p, const float* g, float* m, float* v, float* e, long n4, long n, float lr, float b1,
+                                                float b2, float eps, float wd, float bc1, float rsqrt_bc2, float gscale, float omd) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    float4 pp = *reinterpret_cast<const float4*>(p + i * 4), gg = *reinterpret_cast<const float4*>(g + i * 4);
+    float4 mm = *reinterpret_cast<const float4*>(m + i * 4), vv = *reinterpret_cast<const float4*>(v + i * 4);
+    float4 ee = *reinterpret_cast<const float4*>(e + i * 4);
+    float* P = &pp.x; float* Gv = &gg.x; float* Mv = &mm.x; float* Vv = &vv.x; float* Ev = &ee.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      adamw_elem(P[k], Gv[k], Mv[k], Vv[k], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
+      Ev[k] = ema_elem(Ev[k], P[k], omd);
+    }
+    *reinterpret_cast<float4*>(p + i * 4) = pp; *reinterpret_cast<float4*>(m + i * 4) = mm; *reinterpret_cast<float4*>(v + i * 4) = vv;
+    *reinterpret_cast<float4*>(e + i * 4) = ee;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {                      // adamw_sweep's tail, through memory, then the average
+    const long i = n4 * 4 + threadIdx.x;
+    const float gr = g[i] * gscale;
+    float w = p[i] * (1.f - lr * wd);
+    m[i] = b1 * m[i] + (1.f - b1) * gr;
+    v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
+    w -= (lr / bc1) * (m[i] / (sqrtf(v[i]) * rsqrt_bc2 + eps));
+    p[i] = w;
+    e[i] = ema_elem(e[i], w, omd);
   }
 }
 

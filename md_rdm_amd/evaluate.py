@@ -75,6 +75,7 @@ class CropNameParser(ArgumentParser):
 def build_parser():
     p = CropNameParser("md_rdm_amd.evaluate", description="Score a checkpoint on the NYU val / test split, on the MI355X-native stack")
     p.add_argument("--checkpoint", type=str, default=None, help="Lightning .ckpt or state_dict; without it the hash-filled model is used (a warning says so)")
+    p.add_argument("--ema", action="store_true", help="load the checkpoint's averaged weights (state_dict_ema, written by md_rdm_amd.train --ema_decay) instead of the live ones")
     p.add_argument("--nyu_path", type=str, default=None, help="directory of raw NYU samples (.h5 / .npz), as for md_rdm_amd.train")
     p.add_argument("--split", type=str, default="val", choices=["val", "test"])
     p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N hash-generated samples instead of --nyu_path")
@@ -169,6 +170,8 @@ def main(argv=None):
         raise SystemExit("md_rdm_amd.evaluate: give --nyu_path DIR or --synthetic N (not both)")
     if args.batch_size < 1:
         raise SystemExit("md_rdm_amd.evaluate: --batch_size must be positive")
+    if args.ema and not args.checkpoint:
+        raise SystemExit("md_rdm_amd.evaluate: --ema needs --checkpoint: the averaged weights are an entry of a checkpoint")
     if args.synthetic < 0:
         raise SystemExit("md_rdm_amd.evaluate: --synthetic must be positive")
     if args.rows_max < 0:
@@ -190,7 +193,10 @@ def main(argv=None):
     from .network.RDM_Net import DepthEstimationNet
     model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
     if args.checkpoint:
-        checkpoint.from_lightning(model, args.checkpoint)
+        try:
+            checkpoint.from_lightning(model, args.checkpoint, ema=args.ema)
+        except checkpoint.NoAveragedWeights as e:                 # --ema on a checkpoint without averaged weights
+            raise SystemExit("md_rdm_amd.evaluate: %s" % e.args[0])
     else:
         if rank == 0:
             print("warning: no --checkpoint: using the deterministic hash-filled weights (filler.fill_state_dict) - the scores mean nothing", flush=True)

@@ -148,6 +148,16 @@ def evaluate(model, batches, metrics, exp_pred=False, return_maps=False, rows_ou
     return (result, torch.cat(maps)) if return_maps else result
 
 
+def ema_decay_at(decay, updates, warmup=True):
+    """The decay of the weight average's next update after ``updates`` updates: ``decay``, or with ``warmup`` min(decay, (1 + u) / (10 + u))
+    (0.1, 2/11, 3/12, ... until ``decay`` takes over), so that a young average follows the weights instead of its seed.  Formed in float64 and
+    rounded once to float32, the value the kernel receives."""
+    d = float(decay)
+    if warmup:
+        d = min(d, (1.0 + updates) / (10.0 + updates))
+    return C.c_float(d).value
+
+
 class FusedAdamW:
     """torch.optim.AdamW(lr) semantics (module.py:41) as one launch per contiguous TRAINABLE range of the model's flat parameter /
     gradient buffers (2 for the reference's live graph) + a tiny torch step for the 4 Weights scalars.
@@ -170,9 +180,23 @@ class FusedAdamW:
     coefficient from the slots themselves, and the small gradients are multiplied by the coefficient that kernel wrote.  Nothing is read
     by the host: ``last_grad_norm`` (the norm before clipping) is a device scalar, and reading it is the caller's synchronisation.  Data
     parallel: the norm must be the reduced gradient's, so clipping waits for every stage (``finish()``) and updates after the last one;
-    with the "reduce_scatter" exchange a rank holds only its shard of the sum, and ``step`` raises."""
+    with the "reduce_scatter" exchange a rank holds only its shard of the sum, and ``step`` raises.
 
-    def __init__(self, model: DepthEstimationNet, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, clip=None):
+    ``ema_decay`` (None = off: the launches, the state and the buffers of before): an exponential moving average of the weights,
+    ema += (1 - d)(w - ema) once per optimiser step (so once per accumulation window) with d = ``ema_decay_at(ema_decay, ema_updates,
+    ema_warmup)``.  ``ema`` is a flat float32 buffer like the moments, seeded at the first ``step()`` with the weights of before that step's
+    update (equal on every data-parallel rank) and advanced by the AdamW launch itself (rdm_adamw_fused_ema, clipped or not: the weight it
+    has just formed is still in registers), so every path through ``_update`` carries it; parameter and moment bytes are those of the step
+    without the average.  The four ``weight_layer`` scalars get float32 averages of their own (``ema_small``), updated in torch.  What this
+    optimiser does not update is not averaged: the relative decoders d_6..d_10 and ``d_1.conv1.*`` are used as they are, and so are the
+    BatchNorm running statistics - the averaged weights run with the LIVE statistics, the ``use_buffers=False`` behaviour of
+    ``torch.optim.swa_utils.AveragedModel``.  ``swap_ema()`` exchanges weights and average in place (one rdm_ema_swap_f32 launch per trainable
+    range, no third buffer); ``with opt.ema_weights():`` does it on entry and again on exit, and inside it ``model.state_dict()``,
+    ``forward``, ``predict`` and ``evaluate`` see the averaged weights while ``step()`` and ``state_dict()`` raise.  With the "reduce_scatter"
+    exchange a rank advances the average of the ranges it owns, and ``ema`` is all-gathered where the moments are: in ``state_dict()`` and
+    before a swap - collectives, so every rank must get there."""
+
+    def __init__(self, model: DepthEstimationNet, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, clip=None, ema_decay=None, ema_warmup=True):
         self.model, self.lr, self.betas, self.eps, self.wd = model, lr, betas, eps, weight_decay
         self.step_count = 0
         self.m = self.v = None
@@ -187,6 +211,13 @@ class FusedAdamW:
         self._folded = self._no_sync = False
         self._hooked = None
         self._slots = self._coef = self._sumsq_ws = None
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f"FusedAdamW: ema_decay must be None or lie in [0, 1] (got {ema_decay!r})")
+        self.ema_decay, self.ema_warmup = None if ema_decay is None else float(ema_decay), bool(ema_warmup)
+        self.ema = self.ema_small = None                           # the averages: allocated at the first step, only when ema_decay is set
+        self.ema_updates = 0
+        self._ema_d = 1.0                                          # this step's decay (ema_decay_at), set by step()
+        self._ema_swapped = False
 
     def zero_grad(self):
         """Opens a window: clears the ``weight_layer`` gradients and forgets whatever the accumulator holds."""
@@ -271,7 +302,13 @@ class FusedAdamW:
         off = C.c_void_p
         for ta, tb in self.trainable_ranges():
             lo, hi = max(a, ta), min(b, tb)
-            if lo < hi and clip is None:
+            if lo < hi and self.ema_decay is not None:            # either step, and the average from the weight it forms
+                _lib.check(L.rdm_adamw_fused_ema(off(flat.data_ptr() + 4 * lo), off(gflat.data_ptr() + 4 * lo), off(self.m.data_ptr() + 4 * lo),
+                                                 off(self.v.data_ptr() + 4 * lo), off(self.ema.data_ptr() + 4 * lo), hi - lo, self.lr, self.betas[0],
+                                                 self.betas[1], self.eps, self.wd, self.step_count, float(grad_scale),
+                                                 None if clip is None else _lib.ptr(self._slots), n_slots if clip is not None else 0,
+                                                 0.0 if clip is None else float(clip), None if clip is None else _lib.ptr(self._coef), self._ema_d, st))
+            elif lo < hi and clip is None:
                 _lib.check(L.rdm_adamw_fused(off(flat.data_ptr() + 4 * lo), off(gflat.data_ptr() + 4 * lo), off(self.m.data_ptr() + 4 * lo),
                                              off(self.v.data_ptr() + 4 * lo), hi - lo, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
                                              self.step_count, float(grad_scale), st))
@@ -320,9 +357,14 @@ class FusedAdamW:
         exactly those of the plain step."""
         from . import _lib
         flat, gflat, _ = self.model._flat
+        if self._ema_swapped:
+            raise _lib.RdmError("FusedAdamW.step inside ema_weights(): the model holds the averaged weights - leave the context (or swap_ema() back) first")
         if self.m is None or self.m.data_ptr() == 0 or self.m.numel() != flat.numel():
             self.m = torch.zeros_like(flat)
             self.v = torch.zeros_like(flat)
+        if self.ema_decay is not None:
+            self._seed_ema()
+            self._ema_d = ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup)
         clip = self.clip if clip is None else clip
         if clip is not None and not float(clip) >= 0.0:
             raise ValueError(f"FusedAdamW.step: clip must be a non-negative norm (got {clip!r})")
@@ -370,14 +412,80 @@ class FusedAdamW:
                 self._scale_small(small_grads, self._coef[0])    # the coefficient the kernel formed from the same slots
         self.model.mark_weights_changed(relative_decoders=False)  # derived bf16 copies are stale now (d_6..d_10 are not in the flat buffer: untouched)
         self.small.step()
+        if self.ema_decay is not None:
+            omd = C.c_float(1.0 - self._ema_d).value              # 1.f - d in float32, as the kernel's host side forms it
+            if omd != 0.0:
+                with torch.no_grad():
+                    for e, p in zip(self.ema_small, self._small_params()):
+                        e.add_((p.detach() - e) * omd)
+            self.ema_updates += 1
+
+    # ---- the weight average ----
+    def _small_params(self):
+        return [p for g in self.small.param_groups for p in g["params"]]
+
+    def _seed_ema(self):
+        """The averages start as copies of the current weights (first step, or a resumed state that held none)."""
+        flat = self.model._flat[0]
+        if self.ema is None or self.ema.numel() != flat.numel() or self.ema.device != flat.device:
+            self.ema = flat.detach().clone()
+            self.ema_small = [p.detach().clone() for p in self._small_params()]
+            self.ema_updates = 0
+
+    def swap_ema(self):
+        """Exchange the live weights and their average in place: one rdm_ema_swap_f32 launch per trainable range between the flat parameters
+        and ``ema``, the ``weight_layer`` scalars in torch, and the derived bf16 copies marked stale.  Twice is the identity, bit for bit.
+        Under the "reduce_scatter" exchange it first all-gathers ``ema`` (a collective: every rank calls it)."""
+        from . import _lib
+        if self.ema_decay is None:
+            raise _lib.RdmError("FusedAdamW.swap_ema: the weight average is off (ema_decay=None)")
+        self._seed_ema()                                           # before any step the average IS the weights
+        flat = self.model._flat[0]
+        if self.sync is not None:
+            self.sync.allgather_shards(self.ema)
+        L, st = _lib.lib(), _lib.stream()
+        for a, b in self.trainable_ranges():
+            _lib.check(L.rdm_ema_swap_f32(C.c_void_p(flat.data_ptr() + 4 * a), C.c_void_p(self.ema.data_ptr() + 4 * a), b - a, st))
+        with torch.no_grad():
+            for e, p in zip(self.ema_small, self._small_params()):
+                live = p.detach().clone()
+                p.copy_(e)
+                e.copy_(live)
+        self._ema_swapped = not self._ema_swapped
+        self.model.mark_weights_changed(relative_decoders=False)
+
+    def ema_weights(self):
+        """Context in which the model holds the averaged weights (validation, export): ``swap_ema()`` on entry and again on exit, also when
+        the body raises.  Afterwards weights and average are bit for bit what they were."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            self.swap_ema()
+            try:
+                yield self
+            finally:
+                self.swap_ema()
+        return scope()
 
     def state_dict(self):
-        """Moments, step and lr (the ``optimizer_states`` entry of a checkpoint)."""
+        """Moments, step and lr (the ``optimizer_states`` entry of a checkpoint); with the weight average on also ``ema``, ``ema_small``,
+        ``ema_updates`` and ``ema_decay``."""
+        if self._ema_swapped:
+            from . import _lib
+            raise _lib.RdmError("FusedAdamW.state_dict inside ema_weights(): weights and average are exchanged - leave the context first")
         if self.sync is not None and self.m is not None:          # "reduce_scatter": each rank holds the moments of its shards only
             self.sync.allgather_shards(self.m)
             self.sync.allgather_shards(self.v)
-        return {"step": self.step_count, "lr": self.lr, "exp_avg": None if self.m is None else self.m.detach().cpu().clone(),
-                "exp_avg_sq": None if self.v is None else self.v.detach().cpu().clone(), "small": self.small.state_dict()}
+        sd = {"step": self.step_count, "lr": self.lr, "exp_avg": None if self.m is None else self.m.detach().cpu().clone(),
+              "exp_avg_sq": None if self.v is None else self.v.detach().cpu().clone(), "small": self.small.state_dict()}
+        if self.ema_decay is not None:
+            if self.sync is not None and self.ema is not None:
+                self.sync.allgather_shards(self.ema)
+            sd.update(ema=None if self.ema is None else self.ema.detach().cpu().clone(),
+                      ema_small=None if self.ema_small is None else [e.detach().cpu().clone() for e in self.ema_small],
+                      ema_updates=self.ema_updates, ema_decay=self.ema_decay)
+        return sd
 
     def load_state_dict(self, sd):
         flat = self.model._flat[0]
@@ -389,6 +497,16 @@ class FusedAdamW:
         self.small.load_state_dict(sd["small"])
         for g in self.small.param_groups:
             g["lr"] = self.lr
+        if self.ema_decay is not None:
+            if sd.get("ema") is not None:                          # (this optimiser's ema_decay holds; the saved one is a record)
+                if sd["ema"].numel() != flat.numel() or len(sd["ema_small"]) != len(self._small_params()):
+                    raise ValueError("optimizer state's weight average does not match the model's flat parameter buffer")
+                self.ema = sd["ema"].to(flat.device).clone()
+                self.ema_small = [e.to(flat.device).clone() for e in sd["ema_small"]]
+                self.ema_updates = int(sd["ema_updates"])
+            else:                                                  # a state from a run without the average: re-seeded at the next step
+                self.ema = self.ema_small = None
+                self.ema_updates = 0
 
 
 def accumulation_windows(batches, k):

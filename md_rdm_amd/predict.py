@@ -34,6 +34,7 @@ def build_parser():
     p = ArgumentParser("md_rdm_amd.predict", description="Depth maps (log relative depth, 128x128) for images, on the MI355X-native stack")
     p.add_argument("inputs", nargs="*", help=".npy / .npz uint8 HxWx3 frames, or image files (needs Pillow)")
     p.add_argument("--checkpoint", type=str, default=None, help="Lightning .ckpt or state_dict; without it the hash-filled model is used (a warning says so)")
+    p.add_argument("--ema", action="store_true", help="load the checkpoint's averaged weights (state_dict_ema, written by md_rdm_amd.train --ema_decay) instead of the live ones")
     p.add_argument("--precision", type=int, default=32, choices=[16, 32], help="32: float32 native plan; 16: bf16 MFMA inference path")
     p.add_argument("--batch_size", type=int, default=8)
     p.add_argument("--size", type=int, nargs=2, default=[226, 226], metavar=("H", "W"), help="network input size (module.py:19 feeds 226x226)")
@@ -111,6 +112,8 @@ def main(argv=None):
         raise SystemExit("md_rdm_amd.predict: give input files or --synthetic N (not both)")
     if args.batch_size < 1:
         raise SystemExit("md_rdm_amd.predict: --batch_size must be positive")
+    if args.ema and not args.checkpoint:
+        raise SystemExit("md_rdm_amd.predict: --ema needs --checkpoint: the averaged weights are an entry of a checkpoint")
     check_png_args(args)
     check_metric_args(args)
     import numpy as np
@@ -125,7 +128,10 @@ def main(argv=None):
     from .network.RDM_Net import DepthEstimationNet
     model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
     if args.checkpoint:
-        checkpoint.from_lightning(model, args.checkpoint)
+        try:
+            checkpoint.from_lightning(model, args.checkpoint, ema=args.ema)
+        except checkpoint.NoAveragedWeights as e:                 # --ema on a checkpoint without averaged weights
+            raise SystemExit("md_rdm_amd.predict: %s" % e.args[0])
     else:
         print("warning: no --checkpoint: using the deterministic hash-filled weights (filler.fill_state_dict) - the maps are not depth", flush=True)
         filler.fill_state_dict(model.state_dict())

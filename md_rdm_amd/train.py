@@ -81,6 +81,10 @@ def build_parser():
                         "still update on every batch")
     parser.add_argument("--gradient_clip_val", type=float, default=0.0, help="V (Lightning's name): clip the gradient's global 2-norm to V before every optimiser step "
                         "(torch.nn.utils.clip_grad_norm_ semantics, inside the fused AdamW launch); 0 (default) = off")
+    parser.add_argument("--ema_decay", type=float, default=None, help="D in [0, 1]: keep an exponential moving average of the weights (ema += (1 - D)(w - ema) per optimiser step, "
+                        "inside the fused AdamW launch); every epoch's validation then runs on the averaged weights, so val_delta1, the plateau scheduler and the best "
+                        "checkpoint follow them, and checkpoints also carry them (state_dict_ema: evaluate / predict --ema); BatchNorm statistics stay the live ones; default off")
+    parser.add_argument("--no_ema_warmup", action="store_true", help="with --ema_decay: use D from the first update on instead of min(D, (1 + u) / (10 + u)) after u updates")
     return parser
 
 
@@ -90,6 +94,8 @@ def main(argv=None):
         raise SystemExit(f"--accumulate_grad_batches must be at least 1 (got {args.accumulate_grad_batches})")
     if not args.gradient_clip_val >= 0:
         raise SystemExit(f"--gradient_clip_val must be non-negative, 0 = off (got {args.gradient_clip_val})")
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay <= 1.0:
+        raise SystemExit(f"--ema_decay must lie in [0, 1] (got {args.ema_decay})")
     if args.precision not in (16, 32):
         raise SystemExit("--precision must be 16 or 32")
     if not args.synthetic and not args.nyu_path:
@@ -144,7 +150,7 @@ def main(argv=None):
     if clip is not None and sync.world > 1 and sync.exchange == "reduce_scatter":
         raise SystemExit("--gradient_clip_val with the reduce_scatter exchange is not built (a rank holds one shard of the reduced gradient, not its global norm): "
                          "use the all_reduce exchange")
-    opt = harness.FusedAdamW(model, lr=args.learning_rate, clip=clip)
+    opt = harness.FusedAdamW(model, lr=args.learning_rate, clip=clip, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
     opt.attach_sync(sync)                                        # data parallel: no exchange on the non-final micro-batches of a window
     K = args.accumulate_grad_batches
     sched = ReduceLROnPlateau(opt, "max", patience=2)
@@ -156,6 +162,8 @@ def main(argv=None):
             best_delta1 = resumed.get("best_val_delta1")
             if rank == 0:
                 print(f"resumed optimiser state at step {opt.step_count}, lr {opt.lr:g}, continuing with epoch {start_epoch}", flush=True)
+                if opt.ema_decay is not None:
+                    print(f"weight average: {'restored after %d updates' % opt.ema_updates if opt.ema is not None else 'none in the checkpoint, seeded from the weights at the next step'}", flush=True)
         elif rank == 0:
             print("resumed WEIGHTS only (the checkpoint carries no fused-optimiser state, e.g. a reference Lightning .ckpt)", flush=True)
     logger = MetricLogger(args.metrics if "delta1" in args.metrics else ["delta1"] + list(args.metrics))
@@ -209,7 +217,9 @@ def main(argv=None):
         model.eval()
         model.set_precision("bf16" if args.precision == 16 else "f32")
         batched_val = None
-        with torch.no_grad():
+        import contextlib
+        # --ema_decay: the whole validation pass, whichever branch, sees the averaged weights (exchanged in place, and back afterwards)
+        with torch.no_grad(), (opt.ema_weights() if opt.ema_decay is not None else contextlib.nullcontext()):
             logger.reset()
             if args.val_batch_size > 1:                          # batched: predict + one fused target / metric launch per batch, one copy at the end
                 if val_loader is not None:
@@ -241,7 +251,8 @@ def main(argv=None):
                 os.remove(best_path)
             best_delta1, best_path = d1, path
         if rank == 0:
-            print(f"epoch {epoch}: {steps * args.batch_size * world / (time.time() - t0):.1f} img/s, val_delta1 {d1:.4f}, lr {opt.lr:g}", flush=True)
+            print(f"epoch {epoch}: {steps * args.batch_size * world / (time.time() - t0):.1f} img/s, val_delta1 {d1:.4f}{' (averaged weights, %d updates)' % opt.ema_updates if opt.ema_decay is not None else ''}, "
+                  f"lr {opt.lr:g}", flush=True)
     if world > 1:
         dist.destroy_process_group()
 
