@@ -207,6 +207,11 @@ _DEPTH_SIGNATURES = {
 }
 DEPTH_OUTSIDE = {"zero": 0, "edge": 1}                       # the `outside` argument of rdm_depth_frames
 
+# include/rdm_cloud.h: point clouds (unprojection, normals, in-order compaction into PLY vertex records), part of librdm_hip.so, declared in a header of its own
+_CLOUD_SIGNATURES = {
+    "rdm_depth_cloud": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(f64), f64, f64, i32, i32, vp, i64, vp, i32, vp]),
+}
+
 _lib = None
 _bench = None
 
@@ -228,7 +233,7 @@ def lib():
             raise RdmError(f"{LIB_PATH} not found - run `python -m md_rdm_amd.build` (hipcc --offload-arch=gfx950). "
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _EMA_SIGNATURES, _DEPTH_SIGNATURES):
+        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _EMA_SIGNATURES, _DEPTH_SIGNATURES, _CLOUD_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -293,6 +298,10 @@ def ema_symbols():
 
 def depth_symbols():
     return list(_DEPTH_SIGNATURES)
+
+
+def cloud_symbols():
+    return list(_CLOUD_SIGNATURES)
 
 
 def check(rc):

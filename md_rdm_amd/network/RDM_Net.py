@@ -783,6 +783,14 @@ class DepthEstimationNet(BaseModel):
         log_map, counts = self.predict(x, return_counts=True, flip=flip)
         return depth.metric_frames(log_map, frame_hw, view=view, counts=counts, **kwargs)
 
+    def predict_cloud(self, x, frame_hw, intrinsics, view=None, rgb=None, normals=False, min_depth=0.0, max_depth=math.inf, step=1, flip=False, **kwargs):
+        """Point clouds for a batch of images: ``predict_metric`` (its float32 plane; ``kwargs`` are its log_scale, sid, offset, outside) followed by
+        ``cloud.point_cloud`` with ``intrinsics`` = (fx, fy, cx, cy) of the (h, w) frame; ``rgb`` (B,h,w,3) uint8 colours the points.  The
+        result is ``point_cloud``'s (records, counts)."""
+        from .. import cloud
+        planes = self.predict_metric(x, frame_hw, view=view, flip=flip, want=("f32",), **kwargs)
+        return cloud.point_cloud(planes["f32"], intrinsics, rgb=rgb, normals=normals, min_depth=min_depth, max_depth=max_depth, step=step)
+
     # ---- the reference forward (RDM_Net.py:70-135) -----------------------------------------
     def forward(self, x):
         bf16 = self.precision == "bf16"

@@ -21,6 +21,15 @@ network saw (``nyu.test_view``; the pixels outside are 0, "no measurement", or w
 (default 0.001: millimetres; 65535 saturates).  ``--png`` then colours the saved metric map.
 
   python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --png16 frame0.npy
+
+``--ply`` (with --metric) also writes ``NAME.ply``: the saved metric frame as a binary little-endian point cloud (md_rdm_amd.cloud, one launch
+per batch), pixels without a measurement or outside ``--min_depth`` / ``--max_depth`` dropped, every ``--ply_step``-th pixel of every
+``--ply_step``-th row, with unit normals facing the camera under ``--ply_normals``.  The camera is ``--camera nyu`` (the default) or
+``--intrinsics FX FY CX CY``, always the intrinsics of the RAW frame: with ``--native`` they are used as they are and the points carry the input
+frame's colours; otherwise they are mapped to the saved frame through the rectangle of the raw frame it shows (``cloud.intrinsics_in_view`` of
+``nyu.test_view``) and the cloud has no colour.  For ``--synthetic`` inputs the raw frame is the network input itself.
+
+  python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --ply --ply_normals frame0.npy
 """
 import os
 import sys
@@ -55,6 +64,13 @@ def build_parser():
     p.add_argument("--outside", type=str, default=None, choices=["zero", "edge"], help="--metric: pixels outside the view are 0 (default) or the map's replicated edge")
     p.add_argument("--png16", action="store_true", help="--metric: also write NAME_depth.png, 16-bit greyscale in steps of --depth_unit")
     p.add_argument("--depth_unit", type=float, default=None, metavar="M", help="--metric: metres per step of the 16-bit PNG (default 0.001)")
+    p.add_argument("--ply", action="store_true", help="--metric: also write NAME.ply, the metric frame as a binary point cloud")
+    p.add_argument("--ply_normals", action="store_true", help="--ply: unit normals facing the camera, from the neighbouring pixels")
+    p.add_argument("--ply_step", type=int, default=None, metavar="N", help="--ply: every N-th pixel of every N-th row (default 1)")
+    p.add_argument("--camera", type=str, default=None, metavar="NAME", help="--ply: a named intrinsics set of the raw frame: nyu (default)")
+    p.add_argument("--intrinsics", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"), help="--ply: pinhole intrinsics of the raw frame, instead of --camera")
+    p.add_argument("--min_depth", type=float, default=None, metavar="M", help="--ply: drop points nearer than M metres (default 0)")
+    p.add_argument("--max_depth", type=float, default=None, metavar="M", help="--ply: drop points farther than M metres (default: no limit)")
     return p
 
 
@@ -83,6 +99,33 @@ def check_metric_args(args):
         raise SystemExit("md_rdm_amd.predict: --sid %s is not one of %s" % (args.sid, ", ".join(SID)))
     if args.depth_unit is not None and not 0 < args.depth_unit < float("inf"):
         raise SystemExit("md_rdm_amd.predict: --depth_unit must be positive and finite (got %r)" % args.depth_unit)
+
+
+def check_ply_args(args):
+    """the --ply flags' own rules; raises SystemExit"""
+    import math
+    if not args.ply:
+        given = [f for f, v in (("--ply_normals", args.ply_normals), ("--ply_step", args.ply_step is not None), ("--camera", args.camera is not None),
+                                ("--intrinsics", args.intrinsics is not None), ("--min_depth", args.min_depth is not None), ("--max_depth", args.max_depth is not None)) if v]
+        if given:
+            raise SystemExit("md_rdm_amd.predict: --ply_normals, --ply_step, --camera, --intrinsics, --min_depth and --max_depth need --ply (got %s)" % " ".join(given))
+        return
+    if not args.metric:
+        raise SystemExit("md_rdm_amd.predict: --ply needs --metric: a point cloud is made of depth in metres")
+    if args.camera is not None and args.intrinsics is not None:
+        raise SystemExit("md_rdm_amd.predict: give --camera or --intrinsics (not both)")
+    from .cloud import INTRINSICS
+    if args.camera is not None and args.camera not in INTRINSICS:
+        raise SystemExit("md_rdm_amd.predict: --camera %s is not one of %s" % (args.camera, ", ".join(INTRINSICS)))
+    if args.intrinsics is not None and not (all(math.isfinite(v) for v in args.intrinsics) and args.intrinsics[0] != 0 and args.intrinsics[1] != 0):
+        raise SystemExit("md_rdm_amd.predict: --intrinsics must be finite with FX and FY not 0 (got %r)" % (args.intrinsics,))
+    if args.ply_step is not None and args.ply_step < 1:
+        raise SystemExit("md_rdm_amd.predict: --ply_step must be positive (got %d)" % args.ply_step)
+    lo, hi = args.min_depth if args.min_depth is not None else 0.0, args.max_depth if args.max_depth is not None else math.inf
+    if not lo >= 0:
+        raise SystemExit("md_rdm_amd.predict: --min_depth must be >= 0 (got %r)" % lo)
+    if not hi >= lo:
+        raise SystemExit("md_rdm_amd.predict: --max_depth must not be below --min_depth (got %r, %r)" % (hi, lo))
 
 
 def load_frame(path):
@@ -116,6 +159,7 @@ def main(argv=None):
         raise SystemExit("md_rdm_amd.predict: --ema needs --checkpoint: the averaged weights are an entry of a checkpoint")
     check_png_args(args)
     check_metric_args(args)
+    check_ply_args(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -123,7 +167,7 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
 
-    from . import checkpoint, filler, viz
+    from . import checkpoint, cloud, filler, viz
     from .dataloaders import nyu
     from .network.RDM_Net import DepthEstimationNet
     model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
@@ -174,6 +218,14 @@ def main(argv=None):
                                           want=("f32", "u16") if args.png16 else ("f32",))
             maps = planes["f32"].unsqueeze(1)
             steps = planes["u16"].cpu().numpy() if args.png16 else None
+            if args.ply:
+                intr = cloud.intrinsics_params(args.intrinsics if args.intrinsics is not None else args.camera or "nyu")
+                if not args.native:                                  # the saved frame shows a rectangle of the raw frame (all of the network input for --synthetic)
+                    intr = cloud.intrinsics_in_view(intr, (0.0, 0.0) + tuple(size) if args.synthetic else nyu.test_view(batch.shape[1:3]), frame)
+                records, counts = cloud.point_cloud(planes["f32"], intr, rgb=rgb if args.native else None, normals=args.ply_normals,
+                                                    min_depth=args.min_depth or 0.0, max_depth=args.max_depth if args.max_depth is not None else float("inf"),
+                                                    step=args.ply_step or 1)
+                ply_counts = counts.cpu().tolist()
         else:
             maps = model.predict(x, linear=args.linear, size=region if args.full_res else None, flip=args.flip)
         out = maps.cpu().numpy()
@@ -190,6 +242,8 @@ def main(argv=None):
                 viz.write_png(stem + ".png", pngs[n])
             if args.metric and args.png16:
                 viz.write_png16(stem + "_depth.png", steps[n])
+            if args.ply:
+                cloud.write_ply(stem + ".ply", records[n], ply_counts[n], args.ply_normals, args.native)
         print("batch of %d: %.1f images/s" % (j - i, (j - i) / dt), flush=True)
         i = j
     return 0
