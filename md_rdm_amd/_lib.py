@@ -212,6 +212,11 @@ _CLOUD_SIGNATURES = {
     "rdm_depth_cloud": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(f64), f64, f64, i32, i32, vp, i64, vp, i32, vp]),
 }
 
+# include/rdm_refine.h: guided depth refinement (joint bilateral filter of a depth frame under its colour frame), part of librdm_hip.so, declared in a header of its own
+_REFINE_SIGNATURES = {
+    "rdm_depth_refine": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, f64, f64, i32, f64, vp, vp, vp]),
+}
+
 _lib = None
 _bench = None
 
@@ -233,7 +238,8 @@ def lib():
             raise RdmError(f"{LIB_PATH} not found - run `python -m md_rdm_amd.build` (hipcc --offload-arch=gfx950). "
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _EMA_SIGNATURES, _DEPTH_SIGNATURES, _CLOUD_SIGNATURES):
+        for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _EMA_SIGNATURES, _DEPTH_SIGNATURES, _CLOUD_SIGNATURES,
+                      _REFINE_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -302,6 +308,10 @@ def depth_symbols():
 
 def cloud_symbols():
     return list(_CLOUD_SIGNATURES)
+
+
+def refine_symbols():
+    return list(_REFINE_SIGNATURES)
 
 
 def check(rc):

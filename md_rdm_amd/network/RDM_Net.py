@@ -775,20 +775,46 @@ class DepthEstimationNet(BaseModel):
                 out = lin if lin is not None else torch.exp(out).float()
             return (out, counts) if return_counts else out
 
-    def predict_metric(self, x, frame_hw, view=None, flip=False, **kwargs):
+    def predict_metric(self, x, frame_hw, view=None, flip=False, refine=None, guide=None, **kwargs):
         """Metric depth frames for a batch of images: ``predict(x, return_counts=True, flip=flip)`` followed by ``depth.metric_frames`` of the
         map and the DORN counts (under ``flip`` the unmirrored pass's) over the (h, w) frame, of which the network saw ``view``.  ``kwargs`` are
-        ``metric_frames``' (log_scale, sid, offset, unit, outside, want); the result is its dict."""
+        ``metric_frames``' (log_scale, sid, offset, unit, outside, want); the result is its dict.
+        ``refine``: a dict of ``refine.joint_bilateral``'s keywords (radius, step, sigma_space, sigma_color, fill), or True for its defaults:
+        the float32 plane of ``metric_frames`` is filtered under ``guide``, the (B,h,w,3) uint8 colour frame of the (h, w) frame, and the
+        returned f32 / u16 planes are the refined ones (``unit`` is the metric one)."""
         from .. import depth
+        if refine is None or refine is False:
+            log_map, counts = self.predict(x, return_counts=True, flip=flip)
+            return depth.metric_frames(log_map, frame_hw, view=view, counts=counts, **kwargs)
+        from .. import refine as rf
+        opts = {} if refine is True else dict(refine) if isinstance(refine, dict) else None
+        if opts is None or any(k not in rf.DEFAULTS for k in opts):
+            raise _lib.RdmError("refine must be True or a dict of %s, got %r" % (", ".join(rf.DEFAULTS), refine))
+        h, w = int(frame_hw[0]), int(frame_hw[1])
+        if guide is None:
+            raise _lib.RdmError("refine needs guide, the (B,h,w,3) uint8 colour frame of the output's geometry")
+        if not isinstance(guide, torch.Tensor) or not guide.is_cuda or guide.dtype != torch.uint8 or tuple(guide.shape) != (x.shape[0], h, w, 3):
+            raise _lib.RdmError("guide must be (%d,%d,%d,3) uint8 on the device, got %s %s" % (
+                x.shape[0], h, w, getattr(guide, "dtype", type(guide)), tuple(getattr(guide, "shape", ()))))
+        want = kwargs.pop("want", ("f32",))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        planes = [k for k in want if k in ("f32", "u16")]
         log_map, counts = self.predict(x, return_counts=True, flip=flip)
-        return depth.metric_frames(log_map, frame_hw, view=view, counts=counts, **kwargs)
+        out = depth.metric_frames(log_map, frame_hw, view=view, counts=counts, want=("f32",) + tuple(k for k in want if k not in ("f32", "u16")), **kwargs)
+        refined = rf.joint_bilateral(out.pop("f32"), guide, unit=kwargs.get("unit", 1e-3), want=planes or ("f32",), **opts)
+        out.update((k, refined[k]) for k in planes)
+        return out
 
-    def predict_cloud(self, x, frame_hw, intrinsics, view=None, rgb=None, normals=False, min_depth=0.0, max_depth=math.inf, step=1, flip=False, **kwargs):
+    def predict_cloud(self, x, frame_hw, intrinsics, view=None, rgb=None, normals=False, min_depth=0.0, max_depth=math.inf, step=1, flip=False, refine=None,
+                      **kwargs):
         """Point clouds for a batch of images: ``predict_metric`` (its float32 plane; ``kwargs`` are its log_scale, sid, offset, outside) followed by
         ``cloud.point_cloud`` with ``intrinsics`` = (fx, fy, cx, cy) of the (h, w) frame; ``rgb`` (B,h,w,3) uint8 colours the points.  The
-        result is ``point_cloud``'s (records, counts)."""
+        result is ``point_cloud``'s (records, counts).  ``refine`` is ``predict_metric``'s, with ``rgb`` (required then) as the guide."""
         from .. import cloud
-        planes = self.predict_metric(x, frame_hw, view=view, flip=flip, want=("f32",), **kwargs)
+        on = not (refine is None or refine is False)
+        if on and rgb is None:
+            raise _lib.RdmError("predict_cloud: refine needs rgb, the guide of the filter")
+        planes = self.predict_metric(x, frame_hw, view=view, flip=flip, want=("f32",), refine=refine, guide=rgb if on else None, **kwargs)
         return cloud.point_cloud(planes["f32"], intrinsics, rgb=rgb, normals=normals, min_depth=min_depth, max_depth=max_depth, step=step)
 
     # ---- the reference forward (RDM_Net.py:70-135) -----------------------------------------

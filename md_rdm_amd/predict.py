@@ -30,6 +30,15 @@ frame's colours; otherwise they are mapped to the saved frame through the rectan
 ``nyu.test_view``) and the cloud has no colour.  For ``--synthetic`` inputs the raw frame is the network input itself.
 
   python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --ply --ply_normals frame0.npy
+
+``--refine`` (with --metric --native) filters the metric frame under the raw input frame before anything is written (md_rdm_amd.refine, a joint
+bilateral filter, one launch per batch): taps whose colour differs from the pixel's get little weight, so the depth edges that the enlargement of the
+128x128 map has smeared move back to the colour edges.  ``--refine_radius R`` / ``--refine_step S`` give (2R + 1)^2 taps at multiples of S pixels
+(R <= 8, S <= 16, R * S <= 24; default 3 and 4), ``--refine_sigma_space`` (default R * S / 2) and ``--refine_sigma_color`` (default 12) the two
+widths; ``--refine_fill`` also fills pixels without a measurement from their valid taps.  The ``.npy``, ``NAME_depth.png`` and ``NAME.ply`` all come
+from the refined planes.  The defaults are a starting point: their effect on depth accuracy has not been measured.
+
+  python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --refine --png16 --ply frame0.npy
 """
 import os
 import sys
@@ -71,6 +80,13 @@ def build_parser():
     p.add_argument("--intrinsics", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"), help="--ply: pinhole intrinsics of the raw frame, instead of --camera")
     p.add_argument("--min_depth", type=float, default=None, metavar="M", help="--ply: drop points nearer than M metres (default 0)")
     p.add_argument("--max_depth", type=float, default=None, metavar="M", help="--ply: drop points farther than M metres (default: no limit)")
+    p.add_argument("--refine", action="store_true", help="--metric --native: filter the metric frame under the input frame (joint bilateral) before it is written")
+    p.add_argument("--refine_radius", type=int, default=None, metavar="R", help="--refine: (2R + 1)^2 taps, 1 <= R <= 8 (default 3)")
+    p.add_argument("--refine_step", type=int, default=None, metavar="S", help="--refine: the taps are S pixels apart, 1 <= S <= 16 and R * S <= 24 (default 4)")
+    p.add_argument("--refine_sigma_space", type=float, default=None, metavar="F", help="--refine: width of the spatial weight in pixels (default R * S / 2)")
+    p.add_argument("--refine_sigma_color", type=float, default=None, metavar="F", help="--refine: width of the colour weight in steps of the 8-bit guide (default 12)")
+    p.add_argument("--refine_fill", action="store_true", help="--refine: pixels without a measurement take the weighted mean of their valid taps; with the default "
+                   "--outside zero the band of such pixels within R * S of the view is filled from inside it")
     return p
 
 
@@ -128,6 +144,34 @@ def check_ply_args(args):
         raise SystemExit("md_rdm_amd.predict: --max_depth must not be below --min_depth (got %r, %r)" % (hi, lo))
 
 
+def check_refine_args(args):
+    """the --refine flags' own rules (the ranges are the library's, include/rdm_refine.h); raises SystemExit"""
+    if not args.refine:
+        given = [f for f, v in (("--refine_radius", args.refine_radius is not None), ("--refine_step", args.refine_step is not None),
+                                ("--refine_sigma_space", args.refine_sigma_space is not None), ("--refine_sigma_color", args.refine_sigma_color is not None),
+                                ("--refine_fill", args.refine_fill)) if v]
+        if given:
+            raise SystemExit("md_rdm_amd.predict: --refine_radius, --refine_step, --refine_sigma_space, --refine_sigma_color and --refine_fill need --refine (got %s)" % " ".join(given))
+        return
+    if not (args.metric and args.native):
+        raise SystemExit("md_rdm_amd.predict: --refine needs --metric --native: the guide is the raw frame, which only that mode has at the output's geometry")
+    from .refine import DEFAULTS, check_params
+    bad = check_params(args.refine_radius if args.refine_radius is not None else DEFAULTS["radius"], args.refine_step if args.refine_step is not None else DEFAULTS["step"],
+                       args.refine_sigma_space, args.refine_sigma_color if args.refine_sigma_color is not None else DEFAULTS["sigma_color"])
+    if bad:
+        raise SystemExit("md_rdm_amd.predict: --refine: " + bad)
+
+
+def refine_options(args):
+    """--refine* -> the ``refine`` argument of predict_metric"""
+    if not args.refine:
+        return None
+    opts = {k: v for k, v in (("radius", args.refine_radius), ("step", args.refine_step), ("sigma_space", args.refine_sigma_space), ("sigma_color", args.refine_sigma_color))
+            if v is not None}
+    opts["fill"] = bool(args.refine_fill)
+    return opts
+
+
 def load_frame(path):
     """uint8 (H,W,3)"""
     import numpy as np
@@ -160,6 +204,7 @@ def main(argv=None):
     check_png_args(args)
     check_metric_args(args)
     check_ply_args(args)
+    check_refine_args(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -215,7 +260,7 @@ def main(argv=None):
             frame = batch.shape[1:3] if args.native else region if args.full_res else (128, 128)
             planes = model.predict_metric(x, frame, view=nyu.test_view(frame) if args.native else None, flip=args.flip, sid=args.sid or "nyu",
                                           offset=args.sid_offset or 0.0, unit=args.depth_unit or 1e-3, outside=args.outside or "zero",
-                                          want=("f32", "u16") if args.png16 else ("f32",))
+                                          want=("f32", "u16") if args.png16 else ("f32",), refine=refine_options(args), guide=rgb if args.refine else None)
             maps = planes["f32"].unsqueeze(1)
             steps = planes["u16"].cpu().numpy() if args.png16 else None
             if args.ply:
