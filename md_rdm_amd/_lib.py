@@ -217,6 +217,13 @@ _REFINE_SIGNATURES = {
     "rdm_depth_refine": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, f64, f64, i32, f64, vp, vp, vp]),
 }
 
+# include/rdm_mesh.h: triangle faces of a depth frame (depth-edge-aware, in-order compaction into index records whose vertices are rdm_depth_cloud's), part of librdm_hip.so, declared in a header of its own
+_MESH_SIGNATURES = {
+    "rdm_depth_mesh_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "rdm_depth_mesh": (C.c_int, [vp, i32, i32, i32, f64, f64, i32, f64, i32, vp, i64, vp, vp, vp, i64, vp]),
+}
+MESH_FACES = {"i32": 0, "ply": 1}                            # RDM_MESH_FACES_* (include/rdm_mesh.h)
+
 _lib = None
 _bench = None
 
@@ -239,7 +246,7 @@ def lib():
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _EMA_SIGNATURES, _DEPTH_SIGNATURES, _CLOUD_SIGNATURES,
-                      _REFINE_SIGNATURES):
+                      _REFINE_SIGNATURES, _MESH_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -312,6 +319,10 @@ def cloud_symbols():
 
 def refine_symbols():
     return list(_REFINE_SIGNATURES)
+
+
+def mesh_symbols():
+    return list(_MESH_SIGNATURES)
 
 
 def check(rc):

@@ -2,7 +2,7 @@
 pinhole intrinsics to packed vertex records - position, optionally a unit normal facing the camera, optionally the pixel's colour - with the
 invalid pixels dropped and the rest in row-major order, in ONE launch (``rdm_depth_cloud``, include/rdm_cloud.h), and the binary PLY file around
 those records.  One intrinsics set per call, no lens distortion, and no depth-edge rejection for the normals: a normal across a depth step is
-the normal of the step.
+the normal of the step (the faces of ``md_rdm_amd.mesh``, which index these records, do reject depth edges).
 """
 import ctypes as C
 import math

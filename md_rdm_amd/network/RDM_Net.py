@@ -817,6 +817,20 @@ class DepthEstimationNet(BaseModel):
         planes = self.predict_metric(x, frame_hw, view=view, flip=flip, want=("f32",), refine=refine, guide=rgb if on else None, **kwargs)
         return cloud.point_cloud(planes["f32"], intrinsics, rgb=rgb, normals=normals, min_depth=min_depth, max_depth=max_depth, step=step)
 
+    def predict_mesh(self, x, frame_hw, intrinsics, view=None, rgb=None, normals=False, min_depth=0.0, max_depth=math.inf, step=1, edge_ratio=None, flip=False,
+                     refine=None, **kwargs):
+        """Triangle meshes for a batch of images: ONE ``predict_metric`` call (its float32 plane; ``kwargs`` and ``refine`` as for ``predict_cloud``)
+        followed by ``mesh.depth_mesh`` of that plane: the cloud's records are the vertices, and the faces are the cells of the sampled pixel grid
+        whose depths stay within ``edge_ratio`` of each other (default ``mesh.EDGE_RATIO``, a starting point whose effect has not been measured).
+        The result is ``depth_mesh``'s (records, vertex_counts, faces, face_counts), the payloads of ``mesh.write_ply``."""
+        from .. import mesh
+        on = not (refine is None or refine is False)
+        if on and rgb is None:
+            raise _lib.RdmError("predict_mesh: refine needs rgb, the guide of the filter")
+        planes = self.predict_metric(x, frame_hw, view=view, flip=flip, want=("f32",), refine=refine, guide=rgb if on else None, **kwargs)
+        return mesh.depth_mesh(planes["f32"], intrinsics, rgb=rgb, normals=normals, min_depth=min_depth, max_depth=max_depth, step=step,
+                               edge_ratio=mesh.EDGE_RATIO if edge_ratio is None else edge_ratio)
+
     # ---- the reference forward (RDM_Net.py:70-135) -----------------------------------------
     def forward(self, x):
         bf16 = self.precision == "bf16"

@@ -39,6 +39,14 @@ widths; ``--refine_fill`` also fills pixels without a measurement from their val
 from the refined planes.  The defaults are a starting point: their effect on depth accuracy has not been measured.
 
   python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --refine --png16 --ply frame0.npy
+
+``--mesh`` (with --metric --ply) gives ``NAME.ply`` a face element as well (md_rdm_amd.mesh, two more launches per batch): the pixel grid of the
+saved frame triangulated, two triangles per cell, without the triangles that touch a dropped pixel or whose largest depth exceeds
+``--mesh_edge_ratio R`` times their smallest (R >= 1, default 1.05; ``inf`` keeps every triangle of valid pixels) - the sheets a surface would
+otherwise draw across every depth step.  The vertices are the cloud's points, unchanged; ``--ply_step N`` decimates the mesh with them.  The
+default ratio is a starting point: its effect has not been measured on real predictions.
+
+  python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --refine --ply --ply_normals --mesh --mesh_edge_ratio 1.1 frame0.npy
 """
 import os
 import sys
@@ -87,6 +95,9 @@ def build_parser():
     p.add_argument("--refine_sigma_color", type=float, default=None, metavar="F", help="--refine: width of the colour weight in steps of the 8-bit guide (default 12)")
     p.add_argument("--refine_fill", action="store_true", help="--refine: pixels without a measurement take the weighted mean of their valid taps; with the default "
                    "--outside zero the band of such pixels within R * S of the view is filled from inside it")
+    p.add_argument("--mesh", action="store_true", help="--ply: NAME.ply also carries triangles: the pixel grid without the faces across depth steps")
+    p.add_argument("--mesh_edge_ratio", type=float, default=None, metavar="R", help="--mesh: drop a triangle whose largest depth exceeds R times its smallest, R >= 1 "
+                   "(default 1.05, a starting point; inf keeps all)")
     return p
 
 
@@ -162,6 +173,18 @@ def check_refine_args(args):
         raise SystemExit("md_rdm_amd.predict: --refine: " + bad)
 
 
+def check_mesh_args(args):
+    """the --mesh flags' own rules (the range is the library's, include/rdm_mesh.h); raises SystemExit"""
+    if not args.mesh:
+        if args.mesh_edge_ratio is not None:
+            raise SystemExit("md_rdm_amd.predict: --mesh_edge_ratio needs --mesh")
+        return
+    if not args.ply:
+        raise SystemExit("md_rdm_amd.predict: --mesh needs --ply: the faces go into NAME.ply, behind the cloud's points")
+    if args.mesh_edge_ratio is not None and not args.mesh_edge_ratio >= 1:
+        raise SystemExit("md_rdm_amd.predict: --mesh_edge_ratio must be >= 1 and not NaN (got %r)" % args.mesh_edge_ratio)
+
+
 def refine_options(args):
     """--refine* -> the ``refine`` argument of predict_metric"""
     if not args.refine:
@@ -205,6 +228,7 @@ def main(argv=None):
     check_metric_args(args)
     check_ply_args(args)
     check_refine_args(args)
+    check_mesh_args(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -212,7 +236,7 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
 
-    from . import checkpoint, cloud, filler, viz
+    from . import checkpoint, cloud, filler, mesh, viz
     from .dataloaders import nyu
     from .network.RDM_Net import DepthEstimationNet
     model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
@@ -267,9 +291,14 @@ def main(argv=None):
                 intr = cloud.intrinsics_params(args.intrinsics if args.intrinsics is not None else args.camera or "nyu")
                 if not args.native:                                  # the saved frame shows a rectangle of the raw frame (all of the network input for --synthetic)
                     intr = cloud.intrinsics_in_view(intr, (0.0, 0.0) + tuple(size) if args.synthetic else nyu.test_view(batch.shape[1:3]), frame)
-                records, counts = cloud.point_cloud(planes["f32"], intr, rgb=rgb if args.native else None, normals=args.ply_normals,
-                                                    min_depth=args.min_depth or 0.0, max_depth=args.max_depth if args.max_depth is not None else float("inf"),
-                                                    step=args.ply_step or 1)
+                ply_args = dict(rgb=rgb if args.native else None, normals=args.ply_normals, min_depth=args.min_depth or 0.0,
+                                max_depth=args.max_depth if args.max_depth is not None else float("inf"), step=args.ply_step or 1)
+                if args.mesh:
+                    records, counts, tris, fcounts = mesh.depth_mesh(planes["f32"], intr, edge_ratio=args.mesh_edge_ratio if args.mesh_edge_ratio is not None else mesh.EDGE_RATIO,
+                                                                     **ply_args)
+                    face_counts = fcounts.cpu().tolist()
+                else:
+                    records, counts = cloud.point_cloud(planes["f32"], intr, **ply_args)
                 ply_counts = counts.cpu().tolist()
         else:
             maps = model.predict(x, linear=args.linear, size=region if args.full_res else None, flip=args.flip)
@@ -287,7 +316,9 @@ def main(argv=None):
                 viz.write_png(stem + ".png", pngs[n])
             if args.metric and args.png16:
                 viz.write_png16(stem + "_depth.png", steps[n])
-            if args.ply:
+            if args.ply and args.mesh:
+                mesh.write_ply(stem + ".ply", records[n], ply_counts[n], args.ply_normals, args.native, tris[n], face_counts[n])
+            elif args.ply:
                 cloud.write_ply(stem + ".ply", records[n], ply_counts[n], args.ply_normals, args.native)
         print("batch of %d: %.1f images/s" % (j - i, (j - i) / dt), flush=True)
         i = j
