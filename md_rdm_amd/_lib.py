@@ -224,6 +224,12 @@ _MESH_SIGNATURES = {
 }
 MESH_FACES = {"i32": 0, "ply": 1}                            # RDM_MESH_FACES_* (include/rdm_mesh.h)
 
+# include/rdm_warp.h: novel views of a depth frame (z-buffered forward warp through a 64-bit atomic minimum, row-wise hole fill), part of librdm_hip.so, declared in a header of its own
+_WARP_SIGNATURES = {
+    "rdm_depth_warp_workspace_bytes": (sz, [i32, i32, i32]),
+    "rdm_depth_warp": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(f64), C.POINTER(f64), vp, i32, f64, f64, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+}
+
 _lib = None
 _bench = None
 
@@ -246,7 +252,7 @@ def lib():
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _EMA_SIGNATURES, _DEPTH_SIGNATURES, _CLOUD_SIGNATURES,
-                      _REFINE_SIGNATURES, _MESH_SIGNATURES):
+                      _REFINE_SIGNATURES, _MESH_SIGNATURES, _WARP_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -323,6 +329,10 @@ def refine_symbols():
 
 def mesh_symbols():
     return list(_MESH_SIGNATURES)
+
+
+def warp_symbols():
+    return list(_WARP_SIGNATURES)
 
 
 def check(rc):

@@ -831,6 +831,19 @@ class DepthEstimationNet(BaseModel):
         return mesh.depth_mesh(planes["f32"], intrinsics, rgb=rgb, normals=normals, min_depth=min_depth, max_depth=max_depth, step=step,
                                edge_ratio=mesh.EDGE_RATIO if edge_ratio is None else edge_ratio)
 
+    def predict_view(self, x, frame_hw, intrinsics, pose, view=None, rgb=None, flip=False, refine=None, out_hw=None, intrinsics_out=None, min_depth=0.0,
+                     max_depth=math.inf, splat=1, fill=0, want=("depth", "rgb", "index", "mask"), **kwargs):
+        """The predicted frame seen from another camera: ONE ``predict_metric`` call (its float32 plane; ``kwargs`` and ``refine`` as for
+        ``predict_cloud``) followed by ``warp.render`` of that plane under ``pose`` (source camera -> target camera), with ``intrinsics`` =
+        (fx, fy, cx, cy) of the (h, w) frame and ``rgb`` (B,h,w,3) uint8 as its colours.  The result is ``render``'s dict of planes."""
+        from .. import warp
+        on = not (refine is None or refine is False)
+        if on and rgb is None:
+            raise _lib.RdmError("predict_view: refine needs rgb, the guide of the filter")
+        planes = self.predict_metric(x, frame_hw, view=view, flip=flip, want=("f32",), refine=refine, guide=rgb if on else None, **kwargs)
+        return warp.render(planes["f32"], intrinsics, pose, rgb=rgb, out_hw=out_hw, intrinsics_out=intrinsics_out, min_depth=min_depth, max_depth=max_depth,
+                           splat=splat, fill=fill, want=want)
+
     # ---- the reference forward (RDM_Net.py:70-135) -----------------------------------------
     def forward(self, x):
         bf16 = self.precision == "bf16"

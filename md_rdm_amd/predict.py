@@ -47,6 +47,20 @@ otherwise draw across every depth step.  The vertices are the cloud's points, un
 default ratio is a starting point: its effect has not been measured on real predictions.
 
   python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --refine --ply --ply_normals --mesh --mesh_edge_ratio 1.1 frame0.npy
+
+``--stereo M`` (with --metric) also writes ``NAME_right.png``: the saved frame and its colours seen from a camera M metres to the right
+(md_rdm_amd.warp, three more launches per batch: a z-buffered forward warp, the nearest surface kept in every pixel) - with the input the right eye
+of a stereo pair; with ``--png16`` also ``NAME_right_depth.png``, the warped depth in steps of ``--depth_unit``.  ``--view_pose`` takes the twelve
+values r00 r01 r02 t0 r10 .. t2 of a pose [R | t] from the saved frame's camera to any other and writes ``NAME_view.png`` (and
+``NAME_view_depth.png``) likewise.  The picture has the saved frame's shape and intrinsics (``--camera`` / ``--intrinsics``, ``--min_depth`` /
+``--max_depth`` as for --ply) and needs the saved frame's colours: ``--native`` for file inputs; for ``--synthetic`` inputs ``--full_res``, which
+saves the frame at the network input's own size, whose values are then the colours.  ``--view_splat S`` lets every point cover S x S pixels
+(1..4, default 1) and ``--view_fill F`` fills holes of up to about 2F pixels along each row from the farther side (0..64, default 8); pixels no
+point reached stay black.  With ``--refine`` the refined planes are warped.  Both defaults are starting points: their effect has not been measured
+on real predictions.
+
+  python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --stereo 0.06 --png16 frame0.npy
+  python -m md_rdm_amd.predict --synthetic 2 --out maps --metric --full_res --stereo 0.06
 """
 import os
 import sys
@@ -98,6 +112,13 @@ def build_parser():
     p.add_argument("--mesh", action="store_true", help="--ply: NAME.ply also carries triangles: the pixel grid without the faces across depth steps")
     p.add_argument("--mesh_edge_ratio", type=float, default=None, metavar="R", help="--mesh: drop a triangle whose largest depth exceeds R times its smallest, R >= 1 "
                    "(default 1.05, a starting point; inf keeps all)")
+    p.add_argument("--stereo", type=float, default=None, metavar="M", help="--metric, with --native or --synthetic --full_res: also write NAME_right.png, the frame seen "
+                   "from a camera M metres to the right")
+    p.add_argument("--view_pose", type=float, nargs=12, default=None, metavar="P", help="--metric, with --native or --synthetic --full_res: also write NAME_view.png, the frame "
+                   "seen under the pose r00 r01 r02 t0 r10 r11 r12 t1 r20 r21 r22 t2 (saved frame's camera -> the other camera, metres)")
+    p.add_argument("--view_splat", type=int, default=None, metavar="S", help="--stereo / --view_pose: every point covers S x S pixels, 1..4 (default 1, a starting point)")
+    p.add_argument("--view_fill", type=int, default=None, metavar="F", help="--stereo / --view_pose: fill holes from the farther of the nearest pixels within F columns, 0..64 "
+                   "(default 8, a starting point)")
     return p
 
 
@@ -131,13 +152,16 @@ def check_metric_args(args):
 def check_ply_args(args):
     """the --ply flags' own rules; raises SystemExit"""
     import math
+    view = args.stereo is not None or args.view_pose is not None          # the novel views take the camera and the depth range too
     if not args.ply:
-        given = [f for f, v in (("--ply_normals", args.ply_normals), ("--ply_step", args.ply_step is not None), ("--camera", args.camera is not None),
-                                ("--intrinsics", args.intrinsics is not None), ("--min_depth", args.min_depth is not None), ("--max_depth", args.max_depth is not None)) if v]
+        given = [f for f, v in (("--ply_normals", args.ply_normals), ("--ply_step", args.ply_step is not None), ("--camera", args.camera is not None and not view),
+                                ("--intrinsics", args.intrinsics is not None and not view), ("--min_depth", args.min_depth is not None and not view),
+                                ("--max_depth", args.max_depth is not None and not view)) if v]
         if given:
             raise SystemExit("md_rdm_amd.predict: --ply_normals, --ply_step, --camera, --intrinsics, --min_depth and --max_depth need --ply (got %s)" % " ".join(given))
-        return
-    if not args.metric:
+        if not view:
+            return
+    if args.ply and not args.metric:
         raise SystemExit("md_rdm_amd.predict: --ply needs --metric: a point cloud is made of depth in metres")
     if args.camera is not None and args.intrinsics is not None:
         raise SystemExit("md_rdm_amd.predict: give --camera or --intrinsics (not both)")
@@ -185,6 +209,51 @@ def check_mesh_args(args):
         raise SystemExit("md_rdm_amd.predict: --mesh_edge_ratio must be >= 1 and not NaN (got %r)" % args.mesh_edge_ratio)
 
 
+def check_view_args(args):
+    """the --stereo / --view_* flags' own rules (the ranges are the library's, include/rdm_warp.h); raises SystemExit"""
+    import math
+    if args.stereo is None and args.view_pose is None:
+        given = [f for f, v in (("--view_splat", args.view_splat is not None), ("--view_fill", args.view_fill is not None)) if v]
+        if given:
+            raise SystemExit("md_rdm_amd.predict: --view_splat and --view_fill need --stereo or --view_pose (got %s)" % " ".join(given))
+        return
+    if not args.metric:
+        raise SystemExit("md_rdm_amd.predict: --stereo and --view_pose need --metric: a view is rendered from depth in metres")
+    if not (args.native or (args.synthetic and args.full_res)):
+        raise SystemExit("md_rdm_amd.predict: --stereo and --view_pose need the colours of the saved frame: --native for file inputs, --full_res for --synthetic "
+                         "inputs (the frame is then the network input itself)")
+    if args.stereo is not None and not math.isfinite(args.stereo):
+        raise SystemExit("md_rdm_amd.predict: --stereo must be finite (got %r)" % args.stereo)
+    if args.view_pose is not None and not all(math.isfinite(v) for v in args.view_pose):
+        raise SystemExit("md_rdm_amd.predict: --view_pose must be twelve finite values (got %r)" % (args.view_pose,))
+    from .warp import FILL, SPLAT, check_params
+    bad = check_params(args.view_splat if args.view_splat is not None else SPLAT, args.view_fill if args.view_fill is not None else FILL)
+    if bad:
+        raise SystemExit("md_rdm_amd.predict: --view_splat / --view_fill: " + bad)
+
+
+def view_jobs(args):
+    """[(file suffix, (3,4) pose)] of the views asked for"""
+    import numpy as np
+    from . import warp
+    jobs = []
+    if args.stereo is not None:
+        jobs.append(("_right", warp.stereo_pose(args.stereo)))
+    if args.view_pose is not None:
+        jobs.append(("_view", np.asarray(args.view_pose, np.float64).reshape(3, 4)))
+    return jobs
+
+
+def depth_steps(d, unit):
+    """float32 metres -> uint16 steps by the rule include/rdm_depth.h states for its depth_u16 plane, in the arithmetic it states it in: q = D / unit
+    is ONE float64 division of the widened depth (csrc/depthframe.hip's df_quantise divides in float64 too), NaN -> 0, q >= 65535 -> 65535,
+    otherwise rint(q), ties to even.  On the host: the library quantises only while it writes a frame (rdm_depth_frames from a log map,
+    rdm_depth_refine from its filter) and has no entry point that quantises a finished float32 plane such as a warped one."""
+    import numpy as np
+    q = np.nan_to_num(np.asarray(d, np.float64) / unit, nan=0.0, posinf=65535.0)
+    return np.rint(np.clip(q, 0.0, 65535.0)).astype(np.uint16)
+
+
 def refine_options(args):
     """--refine* -> the ``refine`` argument of predict_metric"""
     if not args.refine:
@@ -229,6 +298,7 @@ def main(argv=None):
     check_ply_args(args)
     check_refine_args(args)
     check_mesh_args(args)
+    check_view_args(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -236,7 +306,7 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
 
-    from . import checkpoint, cloud, filler, mesh, viz
+    from . import checkpoint, cloud, filler, mesh, viz, warp
     from .dataloaders import nyu
     from .network.RDM_Net import DepthEstimationNet
     model = DepthEstimationNet(relative_decoders=tuple(args.relative_decoders))
@@ -287,10 +357,20 @@ def main(argv=None):
                                           want=("f32", "u16") if args.png16 else ("f32",), refine=refine_options(args), guide=rgb if args.refine else None)
             maps = planes["f32"].unsqueeze(1)
             steps = planes["u16"].cpu().numpy() if args.png16 else None
-            if args.ply:
+            views = view_jobs(args)
+            if args.ply or views:
                 intr = cloud.intrinsics_params(args.intrinsics if args.intrinsics is not None else args.camera or "nyu")
                 if not args.native:                                  # the saved frame shows a rectangle of the raw frame (all of the network input for --synthetic)
                     intr = cloud.intrinsics_in_view(intr, (0.0, 0.0) + tuple(size) if args.synthetic else nyu.test_view(batch.shape[1:3]), frame)
+            rendered = []
+            if views:                                                # --synthetic --full_res: the frame is the network input, whose values in [0, 1) are the colours
+                colours = rgb if args.native else (x.permute(0, 2, 3, 1) * 255.0).clamp(0.0, 255.0).to(torch.uint8).contiguous()
+                for suffix, pose in views:
+                    r = warp.render(planes["f32"], intr, pose, rgb=colours, min_depth=args.min_depth or 0.0, max_depth=args.max_depth if args.max_depth is not None else float("inf"),
+                                    splat=args.view_splat if args.view_splat is not None else warp.SPLAT, fill=args.view_fill if args.view_fill is not None else warp.FILL,
+                                    want=("depth", "rgb") if args.png16 else ("rgb",))
+                    rendered.append((suffix, r["rgb"].cpu().numpy(), depth_steps(r["depth"].cpu().numpy(), args.depth_unit or 1e-3) if args.png16 else None))
+            if args.ply:
                 ply_args = dict(rgb=rgb if args.native else None, normals=args.ply_normals, min_depth=args.min_depth or 0.0,
                                 max_depth=args.max_depth if args.max_depth is not None else float("inf"), step=args.ply_step or 1)
                 if args.mesh:
@@ -316,6 +396,10 @@ def main(argv=None):
                 viz.write_png(stem + ".png", pngs[n])
             if args.metric and args.png16:
                 viz.write_png16(stem + "_depth.png", steps[n])
+            for suffix, pics, dsteps in rendered if args.metric else ():
+                viz.write_png(stem + suffix + ".png", pics[n])
+                if dsteps is not None:
+                    viz.write_png16(stem + suffix + "_depth.png", dsteps[n])
             if args.ply and args.mesh:
                 mesh.write_ply(stem + ".ply", records[n], ply_counts[n], args.ply_normals, args.native, tris[n], face_counts[n])
             elif args.ply:
