@@ -349,6 +349,31 @@ def ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def device_depth(depth, who):
+    """The depth frame every depth-output call takes, (B,h,w) float32 on the device: (detached contiguous tensor, (B, h, w)).  ``who`` names the
+    caller in the error."""
+    import torch
+
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
+        raise RdmError("%s runs on the MI355X only; there is no CPU fallback" % who)
+    if depth.dim() != 3 or depth.dtype != torch.float32 or depth.numel() == 0:
+        raise RdmError("depth must be (B,h,w) float32, got %s %s" % (depth.dtype, tuple(depth.shape)))
+    return depth.detach().contiguous(), tuple(depth.shape)
+
+
+def device_rgb(rgb, B, h, w):
+    """The colour frame of a (B,h,w) depth frame, (B,h,w,3) uint8 on the device, detached and contiguous; None stays None."""
+    import torch
+
+    if rgb is None:
+        return None
+    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
+        raise RdmError("rgb must be on the device; there is no CPU fallback")
+    if rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, h, w, 3):
+        raise RdmError("rgb must be (%d,%d,%d,3) uint8, got %s %s" % (B, h, w, rgb.dtype, tuple(rgb.shape)))
+    return rgb.detach().contiguous()
+
+
 def stream():
     """The caller's current HIP stream.  Through the raw query where this torch has it: ``torch.cuda.current_stream()`` builds a Stream object and asks the
     runtime for the device count on the way (hipGetDeviceCount, ~20 us per call on this stack; ~100 C-ABI calls per training step; the host is two steps

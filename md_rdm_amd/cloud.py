@@ -53,22 +53,12 @@ def point_cloud(depth, intrinsics, rgb=None, normals=False, min_depth=0.0, max_d
     name in ``INTRINSICS``); ``rgb`` (B,h,w,3) uint8 on the device, or None.  A pixel is kept iff its depth is finite, > 0 and inside
     [min_depth, max_depth], and y % step == 0 and x % step == 0.  ``records`` (B, stride) uint8: sample b's first counts[b] * record_bytes(normals,
     rgb is not None) bytes are its records in row-major pixel order, the rest of its row is not written; ``counts`` (B,) int32."""
-    if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
-        raise _lib.RdmError("point_cloud runs on the MI355X only; there is no CPU fallback")
-    if depth.dim() != 3 or depth.dtype != torch.float32 or depth.numel() == 0:
-        raise _lib.RdmError("depth must be (B,h,w) float32, got %s %s" % (depth.dtype, tuple(depth.shape)))
-    B, h, w = depth.shape
-    if rgb is not None:
-        if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
-            raise _lib.RdmError("rgb must be on the device; there is no CPU fallback")
-        if rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, h, w, 3):
-            raise _lib.RdmError("rgb must be (%d,%d,%d,3) uint8, got %s %s" % (B, h, w, rgb.dtype, tuple(rgb.shape)))
-        rgb = rgb.detach().contiguous()
+    d, (B, h, w) = _lib.device_depth(depth, "point_cloud")
+    rgb = _lib.device_rgb(rgb, B, h, w)
     step = int(step)
     if step < 1:
         raise _lib.RdmError("step must be positive, got %d" % step)
     intr = (C.c_double * 4)(*intrinsics_params(intrinsics))
-    d = depth.detach().contiguous()
     stride = -(-h // step) * -(-w // step) * record_bytes(normals, rgb is not None)
     records = torch.empty(B, stride, dtype=torch.uint8, device=d.device)
     counts = torch.empty(B, dtype=torch.int32, device=d.device)

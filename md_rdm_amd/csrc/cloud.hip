@@ -7,12 +7,12 @@
 // AHEAD of its run itself (a predicate over a depth plane that sits in L2; float4 loads where step == 1), as every workgroup of depthframe.hip
 // recomputes ls_b itself: no workgroup waits for another, there is no look-back, no ticket and no atomic.  Then it walks its run in chunks of one
 // sampled pixel per thread: validity, the record in registers, a ballot / popcount scan over the workgroup, the records to an LDS stage, the
-// stage to memory.  The stage is laid out at the output address's own residue mod 16, so the chunk leaves as aligned 16-byte stores straight
-// from aligned 16-byte LDS reads; the ragged head and tail - whose words the previous chunk, the next one or a neighbouring workgroup may own -
-// leave as byte stores.  Nothing is read back.
+// stage to memory (depthout_dev.h's stream-out: aligned 16-byte stores, the ragged head and tail as bytes).  Nothing is read back.
+// Validity and the unprojection are depthout_dev.h's, shared with mesh.hip (whose vertex numbers are these records' numbers) and warp.hip.
 #include <cmath>
 
 #include "rdm_common.h"
+#include "depthout_dev.h"
 #include "../../include/rdm_cloud.h"
 
 #pragma clang fp contract(off)                      // the float64 arithmetic is the header's, one IEEE operation per step
@@ -33,35 +33,20 @@ struct ClArgs {
   double fx, fy, cx, cy, dmin, dmax;
 };
 
-struct ClP3 {
-  double x, y, z;
-};
+__device__ __forceinline__ DepthPoint cl_point(const ClArgs& a, int y, int x, float d) { return depth_unproject(y, x, d, a.fx, a.fy, a.cx, a.cy); }
 
-__device__ __forceinline__ bool cl_valid(float d, double dmin, double dmax) {
-  return d > 0.0f && d < INFINITY && (double)d >= dmin && (double)d <= dmax;      // NaN fails d > 0
-}
-
-__device__ __forceinline__ ClP3 cl_point(const ClArgs& a, int y, int x, float d) {
-#pragma clang fp contract(off)
-  ClP3 p;
-  p.z = (double)d;
-  p.x = (((double)x - a.cx) * p.z) / a.fx;
-  p.y = (((double)y - a.cy) * p.z) / a.fy;
-  return p;
-}
-
-__device__ __forceinline__ ClP3 cl_sub(const ClP3& u, const ClP3& v) {
+__device__ __forceinline__ DepthPoint cl_sub(const DepthPoint& u, const DepthPoint& v) {
 #pragma clang fp contract(off)
   return {u.x - v.x, u.y - v.y, u.z - v.z};
 }
 
 // the difference along one axis from the neighbours at -1 (lo) and +1 (hi); false: neither is valid
-__device__ __forceinline__ bool cl_diff(const ClArgs& a, const float* __restrict__ p, const ClP3& P, int y, int x, int dy, int dx, ClP3& out) {
+__device__ __forceinline__ bool cl_diff(const ClArgs& a, const float* __restrict__ p, const DepthPoint& P, int y, int x, int dy, int dx, DepthPoint& out) {
   const int yl = y - dy, xl = x - dx, yh = y + dy, xh = x + dx;
   float dl = 0.0f, dh = 0.0f;
   bool vl = false, vh = false;
-  if (yl >= 0 && xl >= 0) dl = p[yl * a.w + xl], vl = cl_valid(dl, a.dmin, a.dmax);
-  if (yh < a.h && xh < a.w) dh = p[yh * a.w + xh], vh = cl_valid(dh, a.dmin, a.dmax);
+  if (yl >= 0 && xl >= 0) dl = p[yl * a.w + xl], vl = depth_valid(dl, a.dmin, a.dmax);
+  if (yh < a.h && xh < a.w) dh = p[yh * a.w + xh], vh = depth_valid(dh, a.dmin, a.dmax);
   if (vl && vh)
     out = cl_sub(cl_point(a, yh, xh, dh), cl_point(a, yl, xl, dl));
   else if (vh)
@@ -71,10 +56,10 @@ __device__ __forceinline__ bool cl_diff(const ClArgs& a, const float* __restrict
   return vl || vh;
 }
 
-__device__ __forceinline__ void cl_normal(const ClArgs& a, const float* __restrict__ p, const ClP3& P, int y, int x, float n[3]) {
+__device__ __forceinline__ void cl_normal(const ClArgs& a, const float* __restrict__ p, const DepthPoint& P, int y, int x, float n[3]) {
 #pragma clang fp contract(off)
   n[0] = n[1] = n[2] = 0.0f;
-  ClP3 da, db;
+  DepthPoint da, db;
   const bool ha = cl_diff(a, p, P, y, x, 0, 1, da), hb = cl_diff(a, p, P, y, x, 1, 0, db);
   if (!(ha && hb)) return;
   double nx = db.y * da.z - db.z * da.y;
@@ -87,40 +72,28 @@ __device__ __forceinline__ void cl_normal(const ClArgs& a, const float* __restri
   n[0] = (float)(nx / l), n[1] = (float)(ny / l), n[2] = (float)(nz / l);
 }
 
-// block_sum_bcast (postproc_dev.h) for an integer count
-__device__ __forceinline__ int cl_block_sum_bcast(int v, int* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[wv] = v;
-  __syncthreads();
-  int r = 0;
-  for (int i = 0; i < CL_THREADS / 64; ++i) r += sh[i];
-  return r;
-}
-
 // valid pixels among the sampled pixels [0, n) of the plane p, in row-major order
 __device__ __forceinline__ int cl_count_ahead(const ClArgs& a, const float* __restrict__ p, int n, int* sh) {
   const int tid = threadIdx.x;
   int c = 0;
   if (a.step == 1) {                                 // the first n pixels of the plane: scalars up to a 16-byte boundary, float4, scalars
     const int head = min(n, (int)(((16 - ((uintptr_t)p & 15)) & 15) >> 2));
-    if (tid < head) c += cl_valid(p[tid], a.dmin, a.dmax);
+    if (tid < head) c += depth_valid(p[tid], a.dmin, a.dmax);
     const float4* __restrict__ q = (const float4*)(p + head);
     const int nv = (n - head) >> 2;
     for (int i = tid; i < nv; i += CL_THREADS) {
       const float4 v = q[i];
-      c += (int)cl_valid(v.x, a.dmin, a.dmax) + (int)cl_valid(v.y, a.dmin, a.dmax) + (int)cl_valid(v.z, a.dmin, a.dmax) + (int)cl_valid(v.w, a.dmin, a.dmax);
+      c += (int)depth_valid(v.x, a.dmin, a.dmax) + (int)depth_valid(v.y, a.dmin, a.dmax) + (int)depth_valid(v.z, a.dmin, a.dmax) + (int)depth_valid(v.w, a.dmin, a.dmax);
     }
     const int t0 = head + nv * 4;                    // fewer than four are left
-    if (t0 + tid < n) c += cl_valid(p[t0 + tid], a.dmin, a.dmax);
+    if (t0 + tid < n) c += depth_valid(p[t0 + tid], a.dmin, a.dmax);
   } else {
     for (int i = tid; i < n; i += CL_THREADS) {
       const int ry = i / a.sw, rx = i - ry * a.sw;
-      c += cl_valid(p[ry * a.step * a.w + rx * a.step], a.dmin, a.dmax);
+      c += depth_valid(p[ry * a.step * a.w + rx * a.step], a.dmin, a.dmax);
     }
   }
-  return cl_block_sum_bcast(c, sh);
+  return block_sum_bcast<CL_THREADS / 64>(c, sh);
 }
 
 __global__ __launch_bounds__(CL_THREADS) void k_depth_cloud(ClArgs a) {
@@ -141,9 +114,9 @@ __global__ __launch_bounds__(CL_THREADS) void k_depth_cloud(ClArgs a) {
     if (s < s1) {
       const int ry = s / a.sw, rx = s - ry * a.sw, y = ry * a.step, x = rx * a.step, at = y * a.w + x;
       const float d = p[at];
-      ok = cl_valid(d, a.dmin, a.dmax);
+      ok = depth_valid(d, a.dmin, a.dmax);
       if (ok) {
-        const ClP3 P = cl_point(a, y, x, d);
+        const DepthPoint P = cl_point(a, y, x, d);
         r[0] = __float_as_uint((float)P.x), r[1] = __float_as_uint((float)P.y), r[2] = __float_as_uint((float)P.z);
         if (a.normals) {
           float n[3];
@@ -191,16 +164,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_depth_cloud(ClArgs a) {
       }
     }
     __syncthreads();
-    const int end = phase + total * rec;             // stage bytes [phase, end) are the chunk
-    uint8_t* gA = g0 - phase;                        // 16-byte aligned; only [g0, g0 + total * rec) is stored to
-    for (int u = tid; u < (end + 15) >> 4; u += CL_THREADS) {
-      const int lo = u * 16, hi = lo + 16;
-      if (lo >= phase && hi <= end) {
-        *(uint4*)(gA + lo) = *(const uint4*)(stage + lo);
-      } else {
-        for (int k = max(lo, phase); k < min(hi, end); ++k) gA[k] = stage[k];
-      }
-    }
+    stage_flush<CL_THREADS>(stage, g0, phase, phase + total * rec);      // stage bytes [phase, phase + total * rec) are the chunk
     written += total;
   }
   if (part == split - 1 && tid == 0) a.count[b] = written;
@@ -217,19 +181,15 @@ extern "C" int rdm_depth_cloud(const float* depth, const uint8_t* rgb, int32_t b
   RDM_CHECK_ARG(intr, "depth_cloud: intr (fx, fy, cx, cy) must not be NULL");
   RDM_CHECK_ARG(records, "depth_cloud: records must not be NULL");
   RDM_CHECK_ARG(count, "depth_cloud: count must not be NULL");
-  RDM_CHECK_ARG(batch > 0 && h > 0 && w > 0, "depth_cloud: need batch, h, w > 0 (got %d, %d, %d)", (int)batch, (int)h, (int)w);
+  if (const int rc = check_frame_shape("depth_cloud", batch, h, w)) return rc;
   RDM_CHECK_ARG(step > 0, "depth_cloud: step must be positive (got %d)", (int)step);
-  RDM_CHECK_ARG(batch <= 65535, "depth_cloud: batch %d is beyond the grid limit 65535", (int)batch);
-  RDM_CHECK_ARG((long)h * w <= 0x7fffffffL, "depth_cloud: h * w (%d x %d) is beyond the kernel's 32-bit index", (int)h, (int)w);
   RDM_CHECK_ARG(normals == 0 || normals == 1, "depth_cloud: normals must be 0 or 1 (got %d)", (int)normals);
   const int rec = 12 + 12 * normals + (rgb ? 3 : 0);
   const long sh = cdiv(h, step), sw = cdiv(w, step);
   RDM_CHECK_ARG(sample_stride_bytes >= sh * sw * rec && sample_stride_bytes <= 0x7fffffffL,
                 "depth_cloud: sample_stride_bytes %lld must hold %ld x %ld records of %d bytes and stay below 2^31", (long long)sample_stride_bytes, sh, sw, rec);
-  RDM_CHECK_ARG(std::isfinite(intr[0]) && std::isfinite(intr[1]) && std::isfinite(intr[2]) && std::isfinite(intr[3]) && intr[0] != 0 && intr[1] != 0,
-                "depth_cloud: intr (fx %g, fy %g, cx %g, cy %g) must be finite with fx and fy not 0", intr[0], intr[1], intr[2], intr[3]);
-  RDM_CHECK_ARG(min_depth >= 0, "depth_cloud: min_depth must be >= 0 (got %g)", min_depth);
-  RDM_CHECK_ARG(max_depth >= min_depth, "depth_cloud: max_depth (%g) must not be NaN or below min_depth (%g)", max_depth, min_depth);
+  if (const int rc = check_intrinsics("depth_cloud", "intr", intr)) return rc;
+  if (const int rc = check_depth_range("depth_cloud", min_depth, max_depth)) return rc;
   RDM_CHECK_ARG(split >= 0, "depth_cloud: split must be >= 0 (got %d)", (int)split);
   ClArgs a = {};
   a.depth = depth, a.rgb = rgb, a.records = records, a.count = count;

@@ -11,8 +11,8 @@
 // an enlarged frame keeps them for several output rows (480 rows over 128: three to four), so they are kept and recomputed - with the same
 // operations, hence the same bits - only when the row taps move.  What is then left per pixel is one dot4, the add, the float64 exp and the
 // two conversions.  The map itself (128 KiB per sample) is read through the caches: 16 loads per pixel when the taps move, none otherwise.
-// Stores: the quad's float32 as one 16-byte store and its uint16 as one 8-byte store where the address is aligned (always, for a w that is a
-// multiple of 4 in an aligned allocation), otherwise and at the ragged end of a row as scalars.
+// Stores (depthout_dev.h's store_pixels): the quad's float32 as one 16-byte store and its uint16 as one 8-byte store where the address is
+// aligned (always, for a w that is a multiple of 4 in an aligned allocation), otherwise and at the ragged end of a row as scalars.
 #include <cmath>
 
 #include "rdm_common.h"
@@ -39,34 +39,9 @@ struct DfArgs {
   double* scale_out;
 };
 
-struct DfAxis {             // the four taps of one output coordinate: weights, clamped source offsets (elements), centre inside the view
-  double c[4];
-  int o[4];
+struct DfTaps : CubicAxis {             // the taps of one output coordinate (postproc_dev.h) and whether its centre is inside the view
   int inside, pad;
 };
-
-__device__ __forceinline__ void df_axis(int i, double scale, double v0, double v1, int stride, DfAxis& ax) {
-#pragma clang fp contract(off)
-  const double centre = (double)i + 0.5;
-  double t;
-  const int i0 = (int)max(cubic_index_view(scale, centre - v0, DF_SIDE, t), -3L);      // bicubic_at_view
-  cubic_coeffs(t, ax.c);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) ax.o[k] = min(max(i0 - 1 + k, 0), DF_SIDE - 1) * stride;
-  ax.inside = centre >= v0 && centre < v1;
-}
-
-// block_sum_bcast (postproc_dev.h) for the integer counts
-__device__ __forceinline__ long long df_block_sum_bcast(long long v, long long* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[wv] = v;
-  __syncthreads();
-  long long r = 0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-  return r;
-}
 
 __device__ __forceinline__ double df_log_scale(const DfArgs& a, int b, long long* sh) {
 #pragma clang fp contract(off)
@@ -75,7 +50,7 @@ __device__ __forceinline__ double df_log_scale(const DfArgs& a, int b, long long
     const int64_t* c = a.counts + (long)b * a.count_n;
     long long s = 0;
     for (int i = threadIdx.x; i < a.count_n; i += blockDim.x) s += c[i];
-    s = df_block_sum_bcast(s, sh);
+    s = block_sum_bcast(s, sh);
     double x = (double)s / (double)a.count_n;
     x = x + a.offset;
     x = a.Bc * x;
@@ -85,15 +60,8 @@ __device__ __forceinline__ double df_log_scale(const DfArgs& a, int b, long long
   return S + (a.log_scale ? a.log_scale[b] : 0.0);
 }
 
-__device__ __forceinline__ uint16_t df_quantise(double D, double unit) {
-  const double q = D / unit;
-  if (q != q) return 0;
-  if (q >= 65535.0) return 65535;
-  return (uint16_t)(int)rint(q);
-}
-
 __global__ __launch_bounds__(DF_THREADS) void k_depth_frames(DfArgs a) {
-  __shared__ DfAxis rowtab[DF_ROWS];
+  __shared__ DfTaps rowtab[DF_ROWS];
   __shared__ long long red[DF_THREADS / 64];
   const int b = blockIdx.y, part = blockIdx.x, split = gridDim.x, tid = threadIdx.x;
   const int h = a.h, w = a.w;
@@ -111,18 +79,17 @@ __global__ __launch_bounds__(DF_THREADS) void k_depth_frames(DfArgs a) {
   for (int rc = r0; rc < r1; rc += DF_ROWS) {
     const int nr = min(DF_ROWS, r1 - rc);
     __syncthreads();                                 // the previous chunk's readers of rowtab are done
-    if (tid < nr) df_axis(rc + tid, a.sy, a.vy0, a.vy1, DF_SIDE, rowtab[tid]);
+    if (tid < nr) rowtab[tid].inside = cubic_axis_view(rc + tid, a.sy, a.vy0, a.vy1, DF_SIDE, DF_SIDE, rowtab[tid]);
     __syncthreads();
     for (int q = tid; q < quads; q += blockDim.x) {
       const int x0 = q * DF_PX;
-      DfAxis cx[DF_PX];                              // columns past the end of a ragged row get taps too (clamped: valid reads), and are not stored
+      DfTaps cx[DF_PX];                              // columns past the end of a ragged row get taps too (clamped: valid reads), and are not stored
 #pragma unroll
-      for (int p = 0; p < DF_PX; ++p) df_axis(x0 + p, a.sx, a.vx0, a.vx1, 1, cx[p]);
-      const bool full = x0 + DF_PX <= w;
+      for (int p = 0; p < DF_PX; ++p) cx[p].inside = cubic_axis_view(x0 + p, a.sx, a.vx0, a.vx1, DF_SIDE, 1, cx[p]);
       double hrow[DF_PX][4];                         // the x-interpolated map rows ro[0..3] of the quad's pixels
       int ro[4] = {-1, -1, -1, -1};
       for (int r = 0; r < nr; ++r) {
-        const DfAxis ry = rowtab[r];
+        const DfTaps ry = rowtab[r];
         const int y = rc + r;
         float vf[DF_PX];
         uint16_t vu[DF_PX];
@@ -145,7 +112,7 @@ __global__ __launch_bounds__(DF_THREADS) void k_depth_frames(DfArgs a) {
             if (edge || cx[p].inside) {
               const double D = exp(dot4(hrow[p], ry.c) + ls);
               vf[p] = (float)D;
-              vu[p] = df_quantise(D, a.unit);
+              vu[p] = depth_quantise(D, a.unit);
             } else {
               vf[p] = 0.0f, vu[p] = 0;
             }
@@ -155,26 +122,8 @@ __global__ __launch_bounds__(DF_THREADS) void k_depth_frames(DfArgs a) {
           for (int p = 0; p < DF_PX; ++p) vf[p] = 0.0f, vu[p] = 0;
         }
         const long at = (long)y * w + x0;
-        if (f32) {
-          float* d = f32 + at;
-          if (full && ((uintptr_t)d & 15) == 0) {
-            *(float4*)d = make_float4(vf[0], vf[1], vf[2], vf[3]);
-          } else {
-#pragma unroll
-            for (int p = 0; p < DF_PX; ++p)
-              if (x0 + p < w) d[p] = vf[p];
-          }
-        }
-        if (u16) {
-          uint16_t* d = u16 + at;
-          if (full && ((uintptr_t)d & 7) == 0) {
-            *(uint2*)d = make_uint2((uint32_t)vu[0] | (uint32_t)vu[1] << 16, (uint32_t)vu[2] | (uint32_t)vu[3] << 16);
-          } else {
-#pragma unroll
-            for (int p = 0; p < DF_PX; ++p)
-              if (x0 + p < w) d[p] = vu[p];
-          }
-        }
+        if (f32) store_pixels(f32 + at, vf, x0, w);
+        if (u16) store_pixels(u16 + at, vu, x0, w);
       }
     }
   }
@@ -189,9 +138,7 @@ extern "C" int rdm_depth_frames(const double* log_map, const int64_t* counts, in
                                 double* scale_out, int32_t split, rdm_stream_t stream) {
   RDM_CHECK_ARG(log_map, "depth_frames: log_map must not be NULL");
   RDM_CHECK_ARG(depth_f32 || depth_u16, "depth_frames: depth_f32 and depth_u16 must not both be NULL");
-  RDM_CHECK_ARG(batch > 0 && h > 0 && w > 0, "depth_frames: need batch, h, w > 0 (got %d, %d, %d)", (int)batch, (int)h, (int)w);
-  RDM_CHECK_ARG(batch <= 65535, "depth_frames: batch %d is beyond the grid limit 65535", (int)batch);
-  RDM_CHECK_ARG((long)h * w <= 0x7fffffffL, "depth_frames: h * w (%d x %d) is beyond the kernel's 32-bit index", (int)h, (int)w);
+  if (const int rc = check_frame_shape("depth_frames", batch, h, w)) return rc;
   RDM_CHECK_ARG(!counts || count_n >= 1, "depth_frames: counts need count_n >= 1 (got %d)", (int)count_n);
   RDM_CHECK_ARG(!counts || sid, "depth_frames: counts need sid (alpha, beta, K, offset)");
   DfArgs a = {};
@@ -200,7 +147,7 @@ extern "C" int rdm_depth_frames(const double* log_map, const int64_t* counts, in
                   "depth_frames: sid (alpha %g, beta %g, K %g, offset %g) must be finite with 0 < alpha < beta and K > 0", sid[0], sid[1], sid[2], sid[3]);
     a.A = std::log(sid[0]), a.Bc = std::log(sid[1] / sid[0]), a.K = sid[2], a.offset = sid[3];
   }
-  RDM_CHECK_ARG(std::isfinite(unit) && unit > 0, "depth_frames: unit must be finite and positive (got %g)", unit);
+  if (const int rc = check_depth_unit("depth_frames", unit)) return rc;
   RDM_CHECK_ARG(outside == 0 || outside == 1, "depth_frames: outside must be 0 (invalid) or 1 (replicated edge) (got %d)", (int)outside);
   RDM_CHECK_ARG(split >= 0, "depth_frames: split must be >= 0 (got %d)", (int)split);
   RDM_CHECK_ARG(!view || (std::isfinite(view[0]) && std::isfinite(view[1]) && std::isfinite(view[2]) && std::isfinite(view[3]) && view[2] > 0 && view[3] > 0),

@@ -11,12 +11,14 @@
 //   k_mesh_faces, grid (max(sh - 1, 1), batch): workgroup i sums the (at most sh) table entries ahead of it itself - no workgroup waits for another,
 //     no look-back, no ticket, no atomic - then walks its cell row in chunks of one cell per thread: the four corners, a ballot / popcount scan of
 //     the two pixel rows' validity (the corners' vertex numbers) and of the two candidates (the faces' places), the records to an LDS stage, the
-//     stage to memory as cloud.hip does it: laid out at the output address's own residue mod 16, the interior as aligned 16-byte stores, the ragged
-//     head and tail - whose words a neighbouring row may own - as byte stores.  Nothing is read back.
-// Both kernels decide validity, diagonal and edge test with the same function, so the table and the rows cannot disagree.
+//     stage to memory by depthout_dev.h's stream-out, which cloud.hip uses too: the interior as aligned 16-byte stores, the ragged head and tail -
+//     whose words a neighbouring row may own - as byte stores.  Nothing is read back.
+// Both kernels decide validity (depthout_dev.h's depth_valid, cloud.hip's too: the vertex numbers are its record numbers), diagonal and edge
+// test with the same function, so the table and the rows cannot disagree.
 #include <cmath>
 
 #include "rdm_common.h"
+#include "depthout_dev.h"
 #include "../../include/rdm_mesh.h"
 
 #pragma clang fp contract(off)                      // the float64 arithmetic is the header's, one IEEE operation per step
@@ -39,10 +41,6 @@ struct MsArgs {
   double dmin, dmax, ratio;
 };
 
-__device__ __forceinline__ bool ms_valid(float d, double dmin, double dmax) {
-  return d > 0.0f && d < INFINITY && (double)d >= dmin && (double)d <= dmax;      // NaN fails d > 0: rdm_cloud.h's validity, word for word
-}
-
 __device__ __forceinline__ bool ms_edge_ok(float a, float b, float c, double ratio) {
 #pragma clang fp contract(off)
   const float lo = fminf(a, fminf(b, c)), hi = fmaxf(a, fmaxf(b, c));
@@ -64,20 +62,9 @@ __device__ __forceinline__ int ms_cell(float dA, float dB, float dC, float dD, b
   return m;
 }
 
-// the sums of two per-thread integers over the workgroup, to every thread
-__device__ __forceinline__ void ms_block_sum2(int& u, int& v, int (*sh)[MS_WAVES]) {
-  for (int o = 32; o > 0; o >>= 1) u += __shfl_down(u, o), v += __shfl_down(v, o);
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[0][wv] = u, sh[1][wv] = v;
-  __syncthreads();
-  u = v = 0;
-  for (int i = 0; i < MS_WAVES; ++i) u += sh[0][i], v += sh[1][i];
-}
-
 // grid (sh, batch): the valid sampled pixels of sampled row i and the faces of cell row i
 __global__ __launch_bounds__(MS_THREADS) void k_mesh_count(MsArgs a) {
-  __shared__ int red[2][MS_WAVES];
+  __shared__ int red[2 * MS_WAVES];
   const int i = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const float* __restrict__ r0 = a.depth + (long)b * a.h * a.w + (long)i * a.step * a.w;
   const float* __restrict__ r1 = r0 + (long)a.step * a.w;          // read only where i + 1 < sh
@@ -85,16 +72,16 @@ __global__ __launch_bounds__(MS_THREADS) void k_mesh_count(MsArgs a) {
   int nv = 0, nf = 0;
   for (int j = tid; j < a.sw; j += MS_THREADS) {
     const float dA = r0[(long)j * a.step];
-    const bool vA = ms_valid(dA, a.dmin, a.dmax);
+    const bool vA = depth_valid(dA, a.dmin, a.dmax);
     nv += vA;
     if (cells && j + 1 < a.sw) {
       const float dB = r0[(long)(j + 1) * a.step], dC = r1[(long)j * a.step], dD = r1[(long)(j + 1) * a.step];
       bool ad;
-      const int m = ms_cell(dA, dB, dC, dD, vA, ms_valid(dB, a.dmin, a.dmax), ms_valid(dC, a.dmin, a.dmax), ms_valid(dD, a.dmin, a.dmax), a.ratio, ad);
+      const int m = ms_cell(dA, dB, dC, dD, vA, depth_valid(dB, a.dmin, a.dmax), depth_valid(dC, a.dmin, a.dmax), depth_valid(dD, a.dmin, a.dmax), a.ratio, ad);
       nf += (m & 1) + (m >> 1);
     }
   }
-  ms_block_sum2(nv, nf, red);
+  block_sums_bcast<MS_WAVES>(red, nv, nf);
   if (tid == 0) {
     int32_t* t = a.rows + (long)b * 2 * a.sh;
     t[i] = nv, t[a.sh + i] = nf;
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_mesh_count(MsArgs a) {
 // grid (max(sh - 1, 1), batch): the faces of cell row i, and from the last workgroup of a sample its two counts
 __global__ __launch_bounds__(MS_THREADS) void k_mesh_faces(MsArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[MS_STAGE];
-  __shared__ int red[2][MS_WAVES];
+  __shared__ int red[2 * MS_WAVES];
   __shared__ int wsum[3][MS_WAVES];
   const int i = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int32_t* __restrict__ t = a.rows + (long)b * 2 * a.sh;
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_mesh_faces(MsArgs a) {
 
   int v0 = 0, written = 0;                           // vertices in front of sampled row i, faces in front of cell row i
   for (int k = tid; k < i; k += MS_THREADS) v0 += t[k], written += t[a.sh + k];
-  ms_block_sum2(v0, written, red);
+  block_sums_bcast<MS_WAVES>(red, v0, written);
   int v1 = v0 + t[i];                                // vertices in front of sampled row i + 1
   const int vtotal = v1 + (i + 1 < a.sh ? t[i + 1] : 0);           // of the sample, where this is its last workgroup: row i + 1 is its last row
 
@@ -128,7 +115,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_mesh_faces(MsArgs a) {
     bool vB = false, vD = false;
     if (j < nc) {
       dA = r0[(long)j * a.step], dB = r0[(long)(j + 1) * a.step], dC = r1[(long)j * a.step], dD = r1[(long)(j + 1) * a.step];
-      vA = ms_valid(dA, a.dmin, a.dmax), vB = ms_valid(dB, a.dmin, a.dmax), vC = ms_valid(dC, a.dmin, a.dmax), vD = ms_valid(dD, a.dmin, a.dmax);
+      vA = depth_valid(dA, a.dmin, a.dmax), vB = depth_valid(dB, a.dmin, a.dmax), vC = depth_valid(dC, a.dmin, a.dmax), vD = depth_valid(dD, a.dmin, a.dmax);
       m = ms_cell(dA, dB, dC, dD, vA, vB, vC, vD, a.ratio, ad);
     }
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -166,16 +153,7 @@ __global__ __launch_bounds__(MS_THREADS) void k_mesh_faces(MsArgs a) {
       off += rec;
     }
     __syncthreads();
-    const int end = phase + total * rec;             // stage bytes [phase, end) are the chunk
-    uint8_t* gA = g0 - phase;                        // 16-byte aligned; only [g0, g0 + total * rec) is stored to
-    for (int u = tid; u < (end + 15) >> 4; u += MS_THREADS) {
-      const int lo = u * 16, hi = lo + 16;
-      if (lo >= phase && hi <= end) {
-        *(uint4*)(gA + lo) = *(const uint4*)(stage + lo);
-      } else {
-        for (int k = max(lo, phase); k < min(hi, end); ++k) gA[k] = stage[k];
-      }
-    }
+    stage_flush<MS_THREADS>(stage, g0, phase, phase + total * rec);      // stage bytes [phase, phase + total * rec) are the chunk
     written += total;
   }
   if (i == (int)gridDim.x - 1 && tid == 0) {
@@ -188,12 +166,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_mesh_faces(MsArgs a) {
 
 using namespace rdm;
 
-static bool ms_shape_ok(int32_t batch, int32_t h, int32_t w, int32_t step) {
-  return batch > 0 && h > 0 && w > 0 && step > 0 && batch <= 65535 && (long)h * w <= 0x7fffffffL;
-}
-
 extern "C" int64_t rdm_depth_mesh_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t step) {
-  if (!ms_shape_ok(batch, h, w, step)) return 0;
+  if (!(frame_shape_ok(batch, h, w) && step > 0)) return 0;
   return (int64_t)batch * 2 * cdiv(h, step) * (int64_t)sizeof(int32_t);
 }
 
@@ -203,12 +177,9 @@ extern "C" int rdm_depth_mesh(const float* depth, int32_t batch, int32_t h, int3
   RDM_CHECK_ARG(depth, "depth_mesh: depth must not be NULL");
   RDM_CHECK_ARG(faces, "depth_mesh: faces must not be NULL");
   RDM_CHECK_ARG(face_count, "depth_mesh: face_count must not be NULL");
-  RDM_CHECK_ARG(batch > 0 && h > 0 && w > 0, "depth_mesh: need batch, h, w > 0 (got %d, %d, %d)", (int)batch, (int)h, (int)w);
+  if (const int rc = check_frame_shape("depth_mesh", batch, h, w)) return rc;
   RDM_CHECK_ARG(step > 0, "depth_mesh: step must be positive (got %d)", (int)step);
-  RDM_CHECK_ARG(batch <= 65535, "depth_mesh: batch %d is beyond the grid limit 65535", (int)batch);
-  RDM_CHECK_ARG((long)h * w <= 0x7fffffffL, "depth_mesh: h * w (%d x %d) is beyond the kernel's 32-bit index", (int)h, (int)w);
-  RDM_CHECK_ARG(min_depth >= 0, "depth_mesh: min_depth must be >= 0 (got %g)", min_depth);
-  RDM_CHECK_ARG(max_depth >= min_depth, "depth_mesh: max_depth (%g) must not be NaN or below min_depth (%g)", max_depth, min_depth);
+  if (const int rc = check_depth_range("depth_mesh", min_depth, max_depth)) return rc;
   RDM_CHECK_ARG(edge_ratio >= 1, "depth_mesh: edge_ratio must be >= 1 and not NaN (got %g)", edge_ratio);
   RDM_CHECK_ARG(layout == RDM_MESH_FACES_I32 || layout == RDM_MESH_FACES_PLY, "depth_mesh: layout must be 0 (int32 triples) or 1 (PLY face records) (got %d)", (int)layout);
   const int rec = layout == RDM_MESH_FACES_PLY ? 13 : 12;

@@ -3,6 +3,7 @@
 // values.  Device code only; not part of the C ABI.
 #pragma once
 #include "rdm_common.h"
+#include "depthout_dev.h"                          // block_sum_bcast
 
 namespace rdm {
 
@@ -118,18 +119,39 @@ __device__ __forceinline__ double bicubic_at_view(const T* __restrict__ src, int
   return bicubic_taps(src, h, w, (int)max(iy, -3L), ty, (int)max(ix, -3L), tx);
 }
 
-// sum over the workgroup in a FIXED order (lanes by shuffle, then the wavefronts in sequence), broadcast to every thread
-__device__ __forceinline__ double block_sum_bcast(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[wv] = v;
-  __syncthreads();
-  double r = 0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-  return r;
+// The four taps of one output coordinate, precomputed for a kernel that keeps a row or a column fixed while it walks the other axis: the
+// weights and the clamped source offsets (elements, times `stride`).  cubic_axis is bicubic_at's index and taps (viz.hip), cubic_axis_view
+// bicubic_at_view's for output sample i of a grid whose view starts at v0 (depthframe.hip); it returns whether the sample's centre lies inside
+// the view [v0, v1).  The two index functions stay distinct, as in bicubic_at and bicubic_at_view.
+struct CubicAxis {
+  double c[4];
+  int o[4];
+};
+
+__device__ __forceinline__ void cubic_axis_taps(int i0, double t, int n_in, int stride, CubicAxis& ax) {
+  cubic_coeffs(t, ax.c);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) ax.o[k] = min(max(i0 - 1 + k, 0), n_in - 1) * stride;
 }
 
+__device__ __forceinline__ void cubic_axis(int i, int n_in, int n_out, int stride, CubicAxis& ax) {
+  double t;
+  const int i0 = cubic_index(i, n_in, n_out, t);
+  cubic_axis_taps(i0, t, n_in, stride, ax);
+}
+
+__device__ __forceinline__ bool cubic_axis_view(int i, double scale, double v0, double v1, int n_in, int stride, CubicAxis& ax) {
+#pragma clang fp contract(off)
+  const double centre = (double)i + 0.5;
+  double t;
+  const int i0 = (int)max(cubic_index_view(scale, centre - v0, n_in, t), -3L);
+  cubic_axis_taps(i0, t, n_in, stride, ax);
+  return centre >= v0 && centre < v1;
+}
+
+// the sum over the workgroup in a FIXED order, broadcast to every thread: block_sum_bcast (depthout_dev.h), for double with the wavefront count
+// from blockDim; postproc.hip, predict.hip, evalmetrics.hip and evalstd.hip depend on its bits
+//
 // block_sum_bcast of the FIRST `waves` wavefronts of a larger workgroup (every thread calls it; the others' `v` is ignored): the same
 // order of additions as block_sum_bcast in a workgroup of `waves` wavefronts, so a wide kernel can restate a narrow kernel's sum bit for bit
 __device__ __forceinline__ double head_waves_sum_bcast(double v, double* sh, int waves) {

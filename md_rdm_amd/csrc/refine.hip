@@ -16,11 +16,12 @@
 // guide interleaved in one 8-byte cell put the threads of a row 4 words apart: 2-way conflicts in the 32-bit reads the compiler makes of it.)
 // The E reads are indexed by colour differences: lanes with equal differences share an address (a broadcast), the others may collide; that
 // is data, not layout.
-// Stores: the pair's float32 as one 8-byte store and its uint16 as one 4-byte store where the address is aligned, otherwise and at the ragged
-// end of a row as scalars.
+// Stores (depthout_dev.h's store_pixels): the pair's float32 as one 8-byte store and its uint16 as one 4-byte store where the address is
+// aligned, otherwise and at the ragged end of a row as scalars.
 #include <cmath>
 
 #include "rdm_common.h"
+#include "depthout_dev.h"
 #include "../../include/rdm_refine.h"
 
 #pragma clang fp contract(off)                      // the float64 arithmetic is the header's, one IEEE operation per step
@@ -45,13 +46,6 @@ struct RfArgs {
   double unit;
   double ws[RF_MAX_RADIUS + 1];
 };
-
-__device__ __forceinline__ uint16_t rf_quantise(double D, double unit) {      // df_quantise (depthframe.hip)
-  const double q = D / unit;
-  if (q != q) return 0;
-  if (q >= 65535.0) return 65535;
-  return (uint16_t)(int)rint(q);
-}
 
 __global__ __launch_bounds__(RF_THREADS) void k_depth_refine(RfArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rf_lds[];
@@ -85,7 +79,7 @@ __global__ __launch_bounds__(RF_THREADS) void k_depth_refine(RfArgs a) {
       const long at = (long)gy * w + gx;
       const float d = depth[at];
       const uint8_t* g = guide + at * 3;
-      cd = (d > 0.0f && d < INFINITY) ? d : 0.0f;                                                          // NaN fails d > 0
+      cd = depth_measured(d) ? d : 0.0f;                                                                   // no depth range here, unlike depth_valid
       cg = (uint32_t)g[0] | (uint32_t)g[1] << 8 | (uint32_t)g[2] << 16;
     }
     dcell[cy * lw + cx] = cd;
@@ -140,31 +134,12 @@ __global__ __launch_bounds__(RF_THREADS) void k_depth_refine(RfArgs a) {
     if (ok) {
       const double D = num[p] / den[p];
       vf[p] = (float)D;
-      vu[p] = rf_quantise(D, a.unit);
+      vu[p] = depth_quantise(D, a.unit);
     }
   }
   const long at = (long)b * h * w + (long)y * w + x;
-  const bool full = x + RF_PX <= (unsigned)w;
-  if (a.f32) {
-    float* d = a.f32 + at;
-    if (full && ((uintptr_t)d & 7) == 0) {
-      *(float2*)d = make_float2(vf[0], vf[1]);
-    } else {
-#pragma unroll
-      for (int p = 0; p < RF_PX; ++p)
-        if (x + p < (unsigned)w) d[p] = vf[p];
-    }
-  }
-  if (a.u16) {
-    uint16_t* d = a.u16 + at;
-    if (full && ((uintptr_t)d & 3) == 0) {
-      *(uint32_t*)d = (uint32_t)vu[0] | (uint32_t)vu[1] << 16;
-    } else {
-#pragma unroll
-      for (int p = 0; p < RF_PX; ++p)
-        if (x + p < (unsigned)w) d[p] = vu[p];
-    }
-  }
+  if (a.f32) store_pixels(a.f32 + at, vf, x, (unsigned)w);
+  if (a.u16) store_pixels(a.u16 + at, vu, x, (unsigned)w);
 }
 
 }  // namespace rdm
@@ -178,16 +153,14 @@ extern "C" int rdm_depth_refine(const float* depth, const uint8_t* guide, int32_
   RDM_CHECK_ARG(guide, "depth_refine: guide must not be NULL");
   RDM_CHECK_ARG(out_f32 || out_u16, "depth_refine: out_f32 and out_u16 must not both be NULL");
   RDM_CHECK_ARG(out_f32 != depth, "depth_refine: out_f32 must not be depth: the taps read neighbours, in place is not supported");
-  RDM_CHECK_ARG(batch > 0 && h > 0 && w > 0, "depth_refine: need batch, h, w > 0 (got %d, %d, %d)", (int)batch, (int)h, (int)w);
-  RDM_CHECK_ARG(batch <= 65535, "depth_refine: batch %d is beyond the grid limit 65535", (int)batch);
-  RDM_CHECK_ARG((long)h * w <= 0x7fffffffL, "depth_refine: h * w (%d x %d) is beyond the kernel's 32-bit index", (int)h, (int)w);
+  if (const int rc = check_frame_shape("depth_refine", batch, h, w)) return rc;
   RDM_CHECK_ARG(radius >= 1 && radius <= RF_MAX_RADIUS, "depth_refine: radius must be in [1, %d] (got %d)", RF_MAX_RADIUS, (int)radius);
   RDM_CHECK_ARG(step >= 1 && step <= RF_MAX_STEP, "depth_refine: step must be in [1, %d] (got %d)", RF_MAX_STEP, (int)step);
   RDM_CHECK_ARG(radius * step <= RF_MAX_HALO, "depth_refine: radius * step must not exceed %d (got %d * %d)", RF_MAX_HALO, (int)radius, (int)step);
   RDM_CHECK_ARG(sigma_space > 0, "depth_refine: sigma_space must be positive, +inf allowed (got %g)", sigma_space);        // NaN fails
   RDM_CHECK_ARG(sigma_color > 0, "depth_refine: sigma_color must be positive, +inf allowed (got %g)", sigma_color);
   RDM_CHECK_ARG(fill == 0 || fill == 1, "depth_refine: fill must be 0 or 1 (got %d)", (int)fill);
-  RDM_CHECK_ARG(std::isfinite(unit) && unit > 0, "depth_refine: unit must be finite and positive (got %g)", unit);
+  if (const int rc = check_depth_unit("depth_refine", unit)) return rc;
   RfArgs a = {};
   a.depth = depth, a.guide = guide, a.f32 = out_f32, a.u16 = out_u16;
   a.h = h, a.w = w, a.radius = radius, a.step = step, a.fill = fill;

@@ -52,23 +52,10 @@ struct VizMap {            // one depth panel
   int resize;              // (h, w) differs from the output size
 };
 
-struct VizAxis {           // the four taps of one output coordinate: weights and clamped source offsets (elements)
-  double c[4];
-  int o[4];
-};
-
-__device__ __forceinline__ void viz_axis(int i, int n_in, int n_out, int stride, VizAxis& ax) {
-  double t;
-  const int i0 = cubic_index(i, n_in, n_out, t);
-  cubic_coeffs(t, ax.c);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) ax.o[k] = min(max(i0 - 1 + k, 0), n_in - 1) * stride;
-}
-
 __device__ __forceinline__ double viz_load(const void* p, int is_f64, long i) { return is_f64 ? ((const double*)p)[i] : (double)((const float*)p)[i]; }
 
 // bicubic_at (postproc_dev.h) with the taps precomputed: rows along x first, then the four rows along y
-__device__ __forceinline__ double viz_sample(const void* p, int is_f64, const VizAxis& ry, const VizAxis& cx) {
+__device__ __forceinline__ double viz_sample(const void* p, int is_f64, const CubicAxis& ry, const CubicAxis& cx) {
   double rows[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -96,7 +83,7 @@ __device__ __forceinline__ uint32_t viz_byte(float x) {
 }
 
 struct VizState {
-  __attribute__((aligned(16))) VizAxis rowtab[2][VZ_ROWS];
+  __attribute__((aligned(16))) CubicAxis rowtab[2][VZ_ROWS];
   uint32_t stage[VZ_ROWS][VZ_TILE_DWORDS];
   double red[2][VZ_THREADS / 64];
 };
@@ -123,7 +110,7 @@ __device__ __forceinline__ void viz_sweep(VizState& S, const float* __restrict__
     if (tid < 2 * VZ_ROWS) {
       const int k = tid / VZ_ROWS, r = tid % VZ_ROWS;
       const VizMap mk = k == 0 ? maps[0] : maps[1];
-      if (r < nr && mk.p && mk.resize) viz_axis(rc + r, mk.h, H, mk.w, S.rowtab[k][r]);
+      if (r < nr && mk.p && mk.resize) cubic_axis(rc + r, mk.h, H, mk.w, S.rowtab[k][r]);
     }
     __syncthreads();
     for (int m0 = 0; m0 < M; m0 += VZ_THREADS) {
@@ -134,8 +121,8 @@ __device__ __forceinline__ void viz_sweep(VizState& S, const float* __restrict__
       const bool depth = kind == 0 || kind == 1;
       const VizMap mp = kind == 0 ? maps[0] : maps[1];
       const void* bp = kind == 0 ? base[0] : base[1];
-      VizAxis cx;
-      if (depth && mp.resize) viz_axis(ox, mp.w, W, 1, cx);
+      CubicAxis cx;
+      if (depth && mp.resize) cubic_axis(ox, mp.w, W, 1, cx);
       if (STORE || depth) {
         for (int r = 0; r < nr; ++r) {
           const int oy = rc + r;
@@ -143,7 +130,7 @@ __device__ __forceinline__ void viz_sweep(VizState& S, const float* __restrict__
           if (depth) {
             double v;
             if (mp.resize) {
-              const VizAxis ry = S.rowtab[kind][r];
+              const CubicAxis ry = S.rowtab[kind][r];
               v = viz_sample(bp, mp.is_f64, ry, cx);
             } else {
               v = viz_load(bp, mp.is_f64, (long)oy * W + ox);

@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "rdm_common.h"
+#include "depthout_dev.h"
 #include "../../include/rdm_warp.h"
 
 #pragma clang fp contract(off)                      // the float64 arithmetic is the header's, one IEEE operation per step
@@ -41,10 +42,6 @@ struct WpArgs {
   int h, w, th, tw, pose_stride, splat, fill;
   double fx, fy, cx, cy, fxd, fyd, cxd, cyd, dmin, dmax;
 };
-
-__device__ __forceinline__ bool wp_valid(float d, double dmin, double dmax) {
-  return d > 0.0f && d < INFINITY && (double)d >= dmin && (double)d <= dmax;      // NaN fails d > 0: rdm_cloud.h's validity, word for word
-}
 
 __device__ __forceinline__ bool wp_finite(double v) { return fabs(v) < (double)INFINITY; }      // NaN fails
 
@@ -72,14 +69,12 @@ __global__ __launch_bounds__(WP_THREADS) void k_warp_splat(WpArgs a) {
   const double r00 = T[0], r01 = T[1], r02 = T[2], t0 = T[3], r10 = T[4], r11 = T[5], r12 = T[6], t1 = T[7], r20 = T[8], r21 = T[9], r22 = T[10], t2 = T[11];
   for (long i = (long)blockIdx.x * WP_THREADS + threadIdx.x; i < np; i += (long)gridDim.x * WP_THREADS) {
     const float d = p[i];
-    if (!wp_valid(d, a.dmin, a.dmax)) continue;
+    if (!depth_valid(d, a.dmin, a.dmax)) continue;                     // depthout_dev.h: the pixels and the points of cloud.hip
     const int y = (int)(i / a.w), x = (int)(i - (long)y * a.w);
-    const double Z = (double)d;
-    const double X = (((double)x - a.cx) * Z) / a.fx;
-    const double Y = (((double)y - a.cy) * Z) / a.fy;
-    const double Qx = ((r00 * X + r01 * Y) + r02 * Z) + t0;
-    const double Qy = ((r10 * X + r11 * Y) + r12 * Z) + t1;
-    const double Qz = ((r20 * X + r21 * Y) + r22 * Z) + t2;
+    const DepthPoint P = depth_unproject(y, x, d, a.fx, a.fy, a.cx, a.cy);
+    const double Qx = ((r00 * P.x + r01 * P.y) + r02 * P.z) + t0;
+    const double Qy = ((r10 * P.x + r11 * P.y) + r12 * P.z) + t1;
+    const double Qz = ((r20 * P.x + r21 * P.y) + r22 * P.z) + t2;
     const float zf = (float)Qz;
     const unsigned zbits = __float_as_uint(zf);
     if (!(wp_finite(Qz) && zbits - 1u < 0x7f7fffffu)) continue;      // zf > 0 and finite, decided on its bits: 1 .. 0x7f7fffff, the smallest denormal included
@@ -149,12 +144,8 @@ __global__ __launch_bounds__(WP_THREADS) void k_warp_resolve(WpArgs a) {
 
 using namespace rdm;
 
-static bool wp_target_ok(int32_t batch, int32_t th, int32_t tw) {
-  return batch > 0 && th > 0 && tw > 0 && batch <= 65535 && (long)th * tw <= 0x7fffffffL;
-}
-
 extern "C" size_t rdm_depth_warp_workspace_bytes(int32_t batch, int32_t th, int32_t tw) {
-  if (!wp_target_ok(batch, th, tw)) return 0;
+  if (!frame_shape_ok(batch, th, tw)) return 0;
   return (size_t)batch * (size_t)th * (size_t)tw * 8;
 }
 
@@ -180,12 +171,9 @@ extern "C" int rdm_depth_warp(const float* depth, const uint8_t* rgb, int32_t ba
   const size_t need = rdm_depth_warp_workspace_bytes(batch, th, tw);
   RDM_CHECK_ARG(workspace_bytes >= need, "depth_warp: workspace_bytes %zu is below the %zu bytes rdm_depth_warp_workspace_bytes asks for", workspace_bytes, need);
   RDM_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "depth_warp: workspace must be 8-byte aligned");
-  for (const double* intr : {intr_src, intr_dst})
-    RDM_CHECK_ARG(std::isfinite(intr[0]) && std::isfinite(intr[1]) && std::isfinite(intr[2]) && std::isfinite(intr[3]) && intr[0] != 0 && intr[1] != 0,
-                  "depth_warp: %s (fx %g, fy %g, cx %g, cy %g) must be finite with fx and fy not 0", intr == intr_src ? "intr_src" : "intr_dst", intr[0], intr[1],
-                  intr[2], intr[3]);
-  RDM_CHECK_ARG(min_depth >= 0, "depth_warp: min_depth must be >= 0 (got %g)", min_depth);
-  RDM_CHECK_ARG(max_depth >= min_depth, "depth_warp: max_depth (%g) must not be NaN or below min_depth (%g)", max_depth, min_depth);
+  if (const int rc = check_intrinsics("depth_warp", "intr_src", intr_src)) return rc;
+  if (const int rc = check_intrinsics("depth_warp", "intr_dst", intr_dst)) return rc;
+  if (const int rc = check_depth_range("depth_warp", min_depth, max_depth)) return rc;
   WpArgs a = {};
   a.depth = depth, a.rgb = rgb, a.poses = poses, a.keys = (unsigned long long*)workspace;
   a.depth_out = depth_out, a.rgb_out = rgb_out, a.index_out = index_out, a.mask_out = mask_out;

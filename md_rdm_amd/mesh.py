@@ -30,17 +30,12 @@ def faces(depth, min_depth=0.0, max_depth=math.inf, step=1, edge_ratio=EDGE_RATI
     face_counts[b] * face_bytes(layout) bytes are its faces in row-major cell order, the rest of its row is not written; the indices are record
     numbers of ``point_cloud(depth, ..., min_depth, max_depth, step)``; ``face_counts``, ``vertex_counts`` (B,) int32.  The workspace is
     allocated per call."""
-    if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
-        raise _lib.RdmError("mesh.faces runs on the MI355X only; there is no CPU fallback")
-    if depth.dim() != 3 or depth.dtype != torch.float32 or depth.numel() == 0:
-        raise _lib.RdmError("depth must be (B,h,w) float32, got %s %s" % (depth.dtype, tuple(depth.shape)))
+    d, (B, h, w) = _lib.device_depth(depth, "mesh.faces")
     rec = face_bytes(layout)
-    B, h, w = depth.shape
     step = int(step)
     if step < 1:
         raise _lib.RdmError("step must be positive, got %d" % step)
     L = _lib.lib()
-    d = depth.detach().contiguous()
     stride = 2 * (-(-h // step) - 1) * (-(-w // step) - 1) * rec
     buf = torch.empty(max(B * stride, 1), dtype=torch.uint8, device=d.device)      # a frame without cells (one sampled row or column) still passes a pointer
     fcounts = torch.empty(B, dtype=torch.int32, device=d.device)

@@ -246,7 +246,7 @@ def view_jobs(args):
 
 def depth_steps(d, unit):
     """float32 metres -> uint16 steps by the rule include/rdm_depth.h states for its depth_u16 plane, in the arithmetic it states it in: q = D / unit
-    is ONE float64 division of the widened depth (csrc/depthframe.hip's df_quantise divides in float64 too), NaN -> 0, q >= 65535 -> 65535,
+    is ONE float64 division of the widened depth (csrc/depthout_dev.h's depth_quantise divides in float64 too), NaN -> 0, q >= 65535 -> 65535,
     otherwise rint(q), ties to even.  On the host: the library quantises only while it writes a frame (rdm_depth_frames from a log map,
     rdm_depth_refine from its filter) and has no entry point that quantises a finished float32 plane such as a warped one."""
     import numpy as np

@@ -97,20 +97,10 @@ def render(depth, intrinsics, pose, rgb=None, out_hw=None, intrinsics_out=None, 
             raise _lib.RdmError("%s must be finite with fx and fy not 0, got %r" % (name, vals))
     if not (float(min_depth) >= 0 and float(max_depth) >= float(min_depth)):
         raise _lib.RdmError("need 0 <= min_depth <= max_depth, got %r and %r" % (min_depth, max_depth))
-    if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
-        raise _lib.RdmError("warp.render runs on the MI355X only; there is no CPU fallback")
-    if depth.dim() != 3 or depth.dtype != torch.float32 or depth.numel() == 0:
-        raise _lib.RdmError("depth must be (B,h,w) float32, got %s %s" % (depth.dtype, tuple(depth.shape)))
-    B, h, w = depth.shape
-    if rgb is not None:
-        if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
-            raise _lib.RdmError("rgb must be on the device; there is no CPU fallback")
-        if rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, h, w, 3):
-            raise _lib.RdmError("rgb must be (%d,%d,%d,3) uint8, got %s %s" % (B, h, w, rgb.dtype, tuple(rgb.shape)))
-        rgb = rgb.detach().contiguous()
+    d, (B, h, w) = _lib.device_depth(depth, "warp.render")
+    rgb = _lib.device_rgb(rgb, B, h, w)
     th, tw = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
     L = _lib.lib()
-    d = depth.detach().contiguous()
     if isinstance(pose, torch.Tensor) and pose.is_cuda:          # a pose on the device stays there: widened and cut to its rows on the caller's stream
         p = pose.detach().unsqueeze(0) if pose.dim() == 2 else pose.detach()
         if p.dim() != 3 or tuple(p.shape[1:]) not in ((3, 4), (4, 4)) or p.shape[0] not in (1, B) or p.device != d.device:
