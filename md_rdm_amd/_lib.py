@@ -230,6 +230,15 @@ _WARP_SIGNATURES = {
     "rdm_depth_warp": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(f64), C.POINTER(f64), vp, i32, f64, f64, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
 }
 
+# include/rdm_anchor.h: anchored metric depth (cell sums of the log residuals against a sparse metric frame, the fitted scale and the smoothed correction field, the corrected frames), part of librdm_hip.so, declared in a header of its own
+_ANCHOR_SIGNATURES = {
+    "rdm_depth_anchor_cells": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(f64), i32, f64, f64, f64, vp, vp, vp]),
+    "rdm_depth_anchor_field": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, f64, f64, vp, vp, vp, vp]),
+    "rdm_depth_frames_corrected": (C.c_int, [vp, vp, i32, vp, C.POINTER(f64), i32, i32, i32, C.POINTER(f64), i32, f64, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
+}
+ANCHOR_FIT = {"none": 0, "logmean": 1}                       # RDM_ANCHOR_FIT_* (include/rdm_anchor.h); "median" is formed by md_rdm_amd.anchor from rdm_eval_standard_view_f64
+ANCHOR_MAX_CELLS, ANCHOR_MAX_RADIUS = 5120, 96               # RDM_ANCHOR_MAX_CELLS, RDM_ANCHOR_MAX_RADIUS
+
 _lib = None
 _bench = None
 
@@ -252,7 +261,7 @@ def lib():
                            "There is no CPU/PyTorch fallback for the hot path.")
         L = C.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _VIZ_SIGNATURES, _EVAL_SIGNATURES, _EVAL_VIEW_SIGNATURES, _OPTIM_SIGNATURES, _EMA_SIGNATURES, _DEPTH_SIGNATURES, _CLOUD_SIGNATURES,
-                      _REFINE_SIGNATURES, _MESH_SIGNATURES, _WARP_SIGNATURES):
+                      _REFINE_SIGNATURES, _MESH_SIGNATURES, _WARP_SIGNATURES, _ANCHOR_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)     # AttributeError here = header/library drift: fail loudly
                 fn.restype, fn.argtypes = res, args
@@ -333,6 +342,10 @@ def mesh_symbols():
 
 def warp_symbols():
     return list(_WARP_SIGNATURES)
+
+
+def anchor_symbols():
+    return list(_ANCHOR_SIGNATURES)
 
 
 def check(rc):

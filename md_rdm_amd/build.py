@@ -32,7 +32,7 @@ def _stale(target, deps):
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", f) for f in ("rdm_hip.h", "rdm_viz.h", "rdm_eval.h", "rdm_eval_view.h", "rdm_optim.h", "rdm_ema.h", "rdm_depth.h", "rdm_cloud.h", "rdm_refine.h", "rdm_mesh.h", "rdm_warp.h")]
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", f) for f in ("rdm_hip.h", "rdm_viz.h", "rdm_eval.h", "rdm_eval_view.h", "rdm_optim.h", "rdm_ema.h", "rdm_depth.h", "rdm_cloud.h", "rdm_refine.h", "rdm_mesh.h", "rdm_warp.h", "rdm_anchor.h")]
     jobs = []
     for src in sources():
         obj = os.path.join(OBJ, src[:-4] + ".o")

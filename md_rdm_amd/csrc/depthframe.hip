@@ -13,11 +13,13 @@
 // two conversions.  The map itself (128 KiB per sample) is read through the caches: 16 loads per pixel when the taps move, none otherwise.
 // Stores (depthout_dev.h's store_pixels): the quad's float32 as one 16-byte store and its uint16 as one 8-byte store where the address is
 // aligned (always, for a w that is a multiple of 4 in an aligned allocation), otherwise and at the ragged end of a row as scalars.
+#include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "rdm_common.h"
 #include "postproc_dev.h"
-#include "../../include/rdm_depth.h"
+#include "../../include/rdm_anchor.h"               // rdm_depth.h and the corrected call
 
 namespace rdm {
 
@@ -38,6 +40,28 @@ struct DfArgs {
   uint16_t* u16;
   double* scale_out;
 };
+
+// rdm_depth_frames_corrected (include/rdm_anchor.h): the same kernel with a correction field, bilinear between the cell centres, added in the
+// log domain.  A type of its own, so that the plain call's kernel argument - and with it its code - stays what it was.
+struct DfFieldArgs : DfArgs {
+  const double* field;
+  int gy, gx, cell;
+};
+
+struct DfLerp {                          // one output coordinate between two cells of the field: the clamped cell indices and the weight of the second
+  double t;
+  int i0, i1;
+};
+
+__device__ __forceinline__ void df_lerp_axis(int i, int cell, int n, DfLerp& l) {
+#pragma clang fp contract(off)
+  double u = ((double)i + 0.5) / (double)cell;
+  u = u - 0.5;
+  const double f = floor(u);                         // >= -1 and < n: the conversion is exact
+  l.t = u - f;
+  l.i0 = min(max((int)f, 0), n - 1);
+  l.i1 = min(max((int)f + 1, 0), n - 1);
+}
 
 struct DfTaps : CubicAxis {             // the taps of one output coordinate (postproc_dev.h) and whether its centre is inside the view
   int inside, pad;
@@ -60,8 +84,11 @@ __device__ __forceinline__ double df_log_scale(const DfArgs& a, int b, long long
   return S + (a.log_scale ? a.log_scale[b] : 0.0);
 }
 
-__global__ __launch_bounds__(DF_THREADS) void k_depth_frames(DfArgs a) {
+template <class Args>
+__global__ __launch_bounds__(DF_THREADS) void k_depth_frames(Args a) {
+  constexpr bool FIELD = std::is_same<Args, DfFieldArgs>::value;
   __shared__ DfTaps rowtab[DF_ROWS];
+  __shared__ DfLerp rowlerp[FIELD ? DF_ROWS : 1];
   __shared__ long long red[DF_THREADS / 64];
   const int b = blockIdx.y, part = blockIdx.x, split = gridDim.x, tid = threadIdx.x;
   const int h = a.h, w = a.w;
@@ -80,12 +107,19 @@ __global__ __launch_bounds__(DF_THREADS) void k_depth_frames(DfArgs a) {
     const int nr = min(DF_ROWS, r1 - rc);
     __syncthreads();                                 // the previous chunk's readers of rowtab are done
     if (tid < nr) rowtab[tid].inside = cubic_axis_view(rc + tid, a.sy, a.vy0, a.vy1, DF_SIDE, DF_SIDE, rowtab[tid]);
+    if constexpr (FIELD)
+      if (tid < nr) df_lerp_axis(rc + tid, a.cell, a.gy, rowlerp[tid]);
     __syncthreads();
     for (int q = tid; q < quads; q += blockDim.x) {
       const int x0 = q * DF_PX;
       DfTaps cx[DF_PX];                              // columns past the end of a ragged row get taps too (clamped: valid reads), and are not stored
 #pragma unroll
       for (int p = 0; p < DF_PX; ++p) cx[p].inside = cubic_axis_view(x0 + p, a.sx, a.vx0, a.vx1, DF_SIDE, 1, cx[p]);
+      DfLerp lx[FIELD ? DF_PX : 1];
+      if constexpr (FIELD) {
+#pragma unroll
+        for (int p = 0; p < DF_PX; ++p) df_lerp_axis(min(x0 + p, w - 1), a.cell, a.gx, lx[p]);
+      }
       double hrow[DF_PX][4];                         // the x-interpolated map rows ro[0..3] of the quad's pixels
       int ro[4] = {-1, -1, -1, -1};
       for (int r = 0; r < nr; ++r) {
@@ -110,7 +144,16 @@ __global__ __launch_bounds__(DF_THREADS) void k_depth_frames(DfArgs a) {
 #pragma unroll
           for (int p = 0; p < DF_PX; ++p) {
             if (edge || cx[p].inside) {
-              const double D = exp(dot4(hrow[p], ry.c) + ls);
+              double e = dot4(hrow[p], ry.c) + ls;
+              if constexpr (FIELD) {
+                const DfLerp ly = rowlerp[r];
+                const double* __restrict__ f0 = a.field + ((long)b * a.gy + ly.i0) * a.gx;
+                const double* __restrict__ f1 = a.field + ((long)b * a.gy + ly.i1) * a.gx;
+                const double a0 = f0[lx[p].i0], a1 = f1[lx[p].i0];
+                const double top = __builtin_fma(lx[p].t, f0[lx[p].i1] - a0, a0), bot = __builtin_fma(lx[p].t, f1[lx[p].i1] - a1, a1);
+                e = e + __builtin_fma(ly.t, bot - top, top);
+              }
+              const double D = exp(e);
               vf[p] = (float)D;
               vu[p] = depth_quantise(D, a.unit);
             } else {
@@ -133,15 +176,16 @@ __global__ __launch_bounds__(DF_THREADS) void k_depth_frames(DfArgs a) {
 
 using namespace rdm;
 
-extern "C" int rdm_depth_frames(const double* log_map, const int64_t* counts, int32_t count_n, const double* log_scale, const double* sid, int32_t batch,
-                                int32_t h, int32_t w, const double* view, int32_t outside, double unit, float* depth_f32, uint16_t* depth_u16,
-                                double* scale_out, int32_t split, rdm_stream_t stream) {
+// the checks and the launch of both entry points; A: DfArgs, or DfFieldArgs with its own members already set and checked
+template <class A>
+static int depth_frames_launch(A a, const double* log_map, const int64_t* counts, int32_t count_n, const double* log_scale, const double* sid, int32_t batch,
+                               int32_t h, int32_t w, const double* view, int32_t outside, double unit, float* depth_f32, uint16_t* depth_u16,
+                               double* scale_out, int32_t split, rdm_stream_t stream) {
   RDM_CHECK_ARG(log_map, "depth_frames: log_map must not be NULL");
   RDM_CHECK_ARG(depth_f32 || depth_u16, "depth_frames: depth_f32 and depth_u16 must not both be NULL");
   if (const int rc = check_frame_shape("depth_frames", batch, h, w)) return rc;
   RDM_CHECK_ARG(!counts || count_n >= 1, "depth_frames: counts need count_n >= 1 (got %d)", (int)count_n);
   RDM_CHECK_ARG(!counts || sid, "depth_frames: counts need sid (alpha, beta, K, offset)");
-  DfArgs a = {};
   if (counts) {
     RDM_CHECK_ARG(std::isfinite(sid[0]) && std::isfinite(sid[1]) && std::isfinite(sid[2]) && std::isfinite(sid[3]) && sid[0] > 0 && sid[1] > sid[0] && sid[2] > 0,
                   "depth_frames: sid (alpha %g, beta %g, K %g, offset %g) must be finite with 0 < alpha < beta and K > 0", sid[0], sid[1], sid[2], sid[3]);
@@ -162,7 +206,26 @@ extern "C" int rdm_depth_frames(const double* log_map, const int64_t* counts, in
   split = std::min<int>(split, h);
   const int quads = cdiv(w, DF_PX);
   const int threads = std::min(DF_THREADS, std::max(64, cdiv(quads, 64) * 64));
-  hipLaunchKernelGGL(k_depth_frames, dim3(split, batch), dim3(threads), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_depth_frames<A>, dim3(split, batch), dim3(threads), 0, (hipStream_t)stream, a);
   RDM_LAUNCH_OK();
   return RDM_OK;
+}
+
+extern "C" int rdm_depth_frames(const double* log_map, const int64_t* counts, int32_t count_n, const double* log_scale, const double* sid, int32_t batch,
+                                int32_t h, int32_t w, const double* view, int32_t outside, double unit, float* depth_f32, uint16_t* depth_u16,
+                                double* scale_out, int32_t split, rdm_stream_t stream) {
+  return depth_frames_launch(DfArgs{}, log_map, counts, count_n, log_scale, sid, batch, h, w, view, outside, unit, depth_f32, depth_u16, scale_out, split, stream);
+}
+
+extern "C" int rdm_depth_frames_corrected(const double* log_map, const int64_t* counts, int32_t count_n, const double* log_scale, const double* sid,
+                                          int32_t batch, int32_t h, int32_t w, const double* view, int32_t outside, double unit, float* depth_f32,
+                                          uint16_t* depth_u16, double* scale_out, int32_t split, const double* field, int32_t gy, int32_t gx, int32_t cell,
+                                          rdm_stream_t stream) {
+  RDM_CHECK_ARG(field && ((uintptr_t)field & 7) == 0, "depth_frames: field must not be NULL and must be 8-byte aligned");
+  RDM_CHECK_ARG(cell >= 1, "depth_frames: cell must be >= 1 (got %d)", (int)cell);
+  RDM_CHECK_ARG(h <= 0 || w <= 0 || (gy == cdiv(h, cell) && gx == cdiv(w, cell)), "depth_frames: the field's gy x gx (%d x %d) is not ceil(h / cell) x ceil(w / cell) (%d x %d)",
+                (int)gy, (int)gx, cdiv(std::max(h, 1), cell), cdiv(std::max(w, 1), cell));
+  DfFieldArgs a = {};
+  a.field = field, a.gy = gy, a.gx = gx, a.cell = cell;
+  return depth_frames_launch(a, log_map, counts, count_n, log_scale, sid, batch, h, w, view, outside, unit, depth_f32, depth_u16, scale_out, split, stream);
 }

@@ -775,17 +775,38 @@ class DepthEstimationNet(BaseModel):
                 out = lin if lin is not None else torch.exp(out).float()
             return (out, counts) if return_counts else out
 
-    def predict_metric(self, x, frame_hw, view=None, flip=False, refine=None, guide=None, **kwargs):
+    def predict_metric(self, x, frame_hw, view=None, flip=False, refine=None, guide=None, anchors=None, anchor=None, **kwargs):
         """Metric depth frames for a batch of images: ``predict(x, return_counts=True, flip=flip)`` followed by ``depth.metric_frames`` of the
         map and the DORN counts (under ``flip`` the unmirrored pass's) over the (h, w) frame, of which the network saw ``view``.  ``kwargs`` are
         ``metric_frames``' (log_scale, sid, offset, unit, outside, want); the result is its dict.
         ``refine``: a dict of ``refine.joint_bilateral``'s keywords (radius, step, sigma_space, sigma_color, fill), or True for its defaults:
         the float32 plane of ``metric_frames`` is filtered under ``guide``, the (B,h,w,3) uint8 colour frame of the (h, w) frame, and the
-        returned f32 / u16 planes are the refined ones (``unit`` is the metric one)."""
+        returned f32 / u16 planes are the refined ones (``unit`` is the metric one).
+        ``anchors``: a (B,h,w) float32 frame of metric measurements of the (h, w) frame, 0 where there is none (md_rdm_amd.anchor).  The SID
+        scale of the counts (plus ``log_scale``) becomes the prior of ``anchor.fit``, whose keywords ``anchor`` holds (fit, cell, sigma, lam,
+        reject, min_depth, max_depth, field); the frames are ``anchor.metric_frames`` of the fitted scale and field, "log_scale" the fitted one,
+        and ``refine`` filters the anchored plane.  Without ``anchors`` nothing changes."""
         from .. import depth
+        if anchors is None:
+            if anchor is not None:
+                raise _lib.RdmError("predict_metric: the anchor options need anchors, the frame of measurements")
+
+            def frames(log_map, counts, **kw):
+                return depth.metric_frames(log_map, frame_hw, view=view, counts=counts, **kw)
+        else:
+            from .. import anchor as an
+            aopts = {} if anchor is None else dict(anchor) if isinstance(anchor, dict) else None
+            if aopts is None or any(k not in an.DEFAULTS for k in aopts):
+                raise _lib.RdmError("anchor must be a dict of %s, got %r" % (", ".join(an.DEFAULTS), anchor))
+
+            def frames(log_map, counts, log_scale=None, sid="nyu", offset=0.0, **kw):
+                prior = depth.sid_log_scale(counts, sid=sid, offset=offset)
+                if log_scale is not None:
+                    prior = prior + log_scale.reshape(-1)
+                return an.metric_frames(log_map, frame_hw, an.fit(log_map, anchors, view=view, prior=prior, **aopts), view=view, **kw)
         if refine is None or refine is False:
             log_map, counts = self.predict(x, return_counts=True, flip=flip)
-            return depth.metric_frames(log_map, frame_hw, view=view, counts=counts, **kwargs)
+            return frames(log_map, counts, **kwargs)
         from .. import refine as rf
         opts = {} if refine is True else dict(refine) if isinstance(refine, dict) else None
         if opts is None or any(k not in rf.DEFAULTS for k in opts):
@@ -800,14 +821,14 @@ class DepthEstimationNet(BaseModel):
         want = (want,) if isinstance(want, str) else tuple(want)
         planes = [k for k in want if k in ("f32", "u16")]
         log_map, counts = self.predict(x, return_counts=True, flip=flip)
-        out = depth.metric_frames(log_map, frame_hw, view=view, counts=counts, want=("f32",) + tuple(k for k in want if k not in ("f32", "u16")), **kwargs)
+        out = frames(log_map, counts, want=("f32",) + tuple(k for k in want if k not in ("f32", "u16")), **kwargs)
         refined = rf.joint_bilateral(out.pop("f32"), guide, unit=kwargs.get("unit", 1e-3), want=planes or ("f32",), **opts)
         out.update((k, refined[k]) for k in planes)
         return out
 
     def predict_cloud(self, x, frame_hw, intrinsics, view=None, rgb=None, normals=False, min_depth=0.0, max_depth=math.inf, step=1, flip=False, refine=None,
                       **kwargs):
-        """Point clouds for a batch of images: ``predict_metric`` (its float32 plane; ``kwargs`` are its log_scale, sid, offset, outside) followed by
+        """Point clouds for a batch of images: ``predict_metric`` (its float32 plane; ``kwargs`` are its log_scale, sid, offset, outside, anchors, anchor) followed by
         ``cloud.point_cloud`` with ``intrinsics`` = (fx, fy, cx, cy) of the (h, w) frame; ``rgb`` (B,h,w,3) uint8 colours the points.  The
         result is ``point_cloud``'s (records, counts).  ``refine`` is ``predict_metric``'s, with ``rgb`` (required then) as the guide."""
         from .. import cloud

@@ -61,6 +61,20 @@ on real predictions.
 
   python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --stereo 0.06 --png16 frame0.npy
   python -m md_rdm_amd.predict --synthetic 2 --out maps --metric --full_res --stereo 0.06
+
+``--anchors PATH...`` (with --metric --native; for ``--synthetic`` inputs with --full_res) ties every frame to metric measurements of it
+(md_rdm_amd.anchor, three launches per batch): one file per input, in the saved frame's own geometry, a pixel without a measurement 0 - SLAM / SfM
+landmarks rendered into the frame, a LiDAR sweep, a sensor frame with holes.  ``.npy`` files hold float32 metres; 16-bit greyscale PNGs hold steps
+of ``--anchor_unit`` metres (default 0.001) and are read with the standard library.  The SID scale becomes the prior;
+``--anchor_fit logmean`` (the default) adds the mean log residual of the anchors to it, ``median`` replaces it by the ratio of medians
+(``evaluate --align median``'s statistic), ``none`` keeps it.  What the scale leaves is summed over cells of ``--anchor_cell`` pixels (default 16),
+smoothed over ``--anchor_sigma`` cells (default 2) and added as a correction field, pulled to 0 by ``--anchor_lambda`` (default 1, in anchors) where
+there are few anchors; ``--anchor_no_field`` fits the scale alone.  ``--anchor_reject F`` drops anchors whose log residual against the prior exceeds
+F (``median`` makes a prior that outliers do not move).  ``--min_depth`` / ``--max_depth`` bound the anchors too.  The ``.npy``, ``NAME_depth.png``,
+``NAME.ply`` and ``NAME_right.png`` all come from the anchored planes; with ``--refine`` the anchored plane is filtered.  The defaults are starting
+points: their effect on real data has not been measured.
+
+  python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --anchors frame0_lidar.png --anchor_fit median --anchor_reject 0.5 frame0.npy
 """
 import os
 import sys
@@ -119,6 +133,15 @@ def build_parser():
     p.add_argument("--view_splat", type=int, default=None, metavar="S", help="--stereo / --view_pose: every point covers S x S pixels, 1..4 (default 1, a starting point)")
     p.add_argument("--view_fill", type=int, default=None, metavar="F", help="--stereo / --view_pose: fill holes from the farther of the nearest pixels within F columns, 0..64 "
                    "(default 8, a starting point)")
+    p.add_argument("--anchors", type=str, nargs="+", default=None, metavar="PATH", help="--metric --native (or --synthetic --full_res): one frame of metric measurements "
+                   "per input, .npy float32 metres or a 16-bit PNG in steps of --anchor_unit, 0 = no measurement; the frames are fitted to them")
+    p.add_argument("--anchor_fit", type=str, default=None, choices=["logmean", "median", "none"], help="--anchors: how the scale is fitted (default logmean)")
+    p.add_argument("--anchor_cell", type=int, default=None, metavar="N", help="--anchors: side of the correction field's cells in pixels (default 16, a starting point)")
+    p.add_argument("--anchor_sigma", type=float, default=None, metavar="F", help="--anchors: width of the field's smoothing in cells (default 2, a starting point)")
+    p.add_argument("--anchor_lambda", type=float, default=None, metavar="F", help="--anchors: regulariser of the field in anchors (default 1, a starting point)")
+    p.add_argument("--anchor_reject", type=float, default=None, metavar="F", help="--anchors: drop anchors whose log residual against the prior exceeds F (default: none)")
+    p.add_argument("--anchor_unit", type=float, default=None, metavar="M", help="--anchors: metres per step of a 16-bit PNG anchor file (default 0.001)")
+    p.add_argument("--anchor_no_field", action="store_true", help="--anchors: fit the scale only, no correction field")
     return p
 
 
@@ -153,13 +176,14 @@ def check_ply_args(args):
     """the --ply flags' own rules; raises SystemExit"""
     import math
     view = args.stereo is not None or args.view_pose is not None          # the novel views take the camera and the depth range too
+    anchored = args.anchors is not None                                   # ... and the anchors the depth range
     if not args.ply:
         given = [f for f, v in (("--ply_normals", args.ply_normals), ("--ply_step", args.ply_step is not None), ("--camera", args.camera is not None and not view),
-                                ("--intrinsics", args.intrinsics is not None and not view), ("--min_depth", args.min_depth is not None and not view),
-                                ("--max_depth", args.max_depth is not None and not view)) if v]
+                                ("--intrinsics", args.intrinsics is not None and not view), ("--min_depth", args.min_depth is not None and not view and not anchored),
+                                ("--max_depth", args.max_depth is not None and not view and not anchored)) if v]
         if given:
             raise SystemExit("md_rdm_amd.predict: --ply_normals, --ply_step, --camera, --intrinsics, --min_depth and --max_depth need --ply (got %s)" % " ".join(given))
-        if not view:
+        if not view and not anchored:
             return
     if args.ply and not args.metric:
         raise SystemExit("md_rdm_amd.predict: --ply needs --metric: a point cloud is made of depth in metres")
@@ -232,6 +256,60 @@ def check_view_args(args):
         raise SystemExit("md_rdm_amd.predict: --view_splat / --view_fill: " + bad)
 
 
+def check_anchor_args(args):
+    """the --anchor* flags' own rules (the ranges are the library's, include/rdm_anchor.h); raises SystemExit"""
+    import math
+    if args.anchors is None:
+        given = [f for f, v in (("--anchor_fit", args.anchor_fit is not None), ("--anchor_cell", args.anchor_cell is not None), ("--anchor_sigma", args.anchor_sigma is not None),
+                                ("--anchor_lambda", args.anchor_lambda is not None), ("--anchor_reject", args.anchor_reject is not None),
+                                ("--anchor_unit", args.anchor_unit is not None), ("--anchor_no_field", args.anchor_no_field)) if v]
+        if given:
+            raise SystemExit("md_rdm_amd.predict: --anchor_fit, --anchor_cell, --anchor_sigma, --anchor_lambda, --anchor_reject, --anchor_unit and --anchor_no_field need "
+                             "--anchors (got %s)" % " ".join(given))
+        return
+    if not args.metric:
+        raise SystemExit("md_rdm_amd.predict: --anchors needs --metric: the anchors are depth in metres")
+    if not (args.native or (args.synthetic and args.full_res)):
+        raise SystemExit("md_rdm_amd.predict: --anchors needs the saved frame in the anchors' geometry: --native for file inputs, --full_res for --synthetic "
+                         "inputs (the frame is then the network input itself)")
+    n_in = args.synthetic or len(args.inputs)
+    if len(args.anchors) != n_in:
+        raise SystemExit("md_rdm_amd.predict: --anchors takes one file per input (got %d files for %d inputs)" % (len(args.anchors), n_in))
+    if args.anchor_unit is not None and not 0 < args.anchor_unit < math.inf:
+        raise SystemExit("md_rdm_amd.predict: --anchor_unit must be positive and finite (got %r)" % args.anchor_unit)
+    from .anchor import DEFAULTS, check_params
+    bad = check_params(args.anchor_cell if args.anchor_cell is not None else DEFAULTS["cell"], args.anchor_sigma if args.anchor_sigma is not None else DEFAULTS["sigma"],
+                       args.anchor_lambda if args.anchor_lambda is not None else DEFAULTS["lam"], args.anchor_reject)
+    if bad:
+        raise SystemExit("md_rdm_amd.predict: --anchors: " + bad)
+
+
+def anchor_options(args):
+    """--anchor* -> the ``anchor`` argument of predict_metric"""
+    opts = {k: v for k, v in (("fit", args.anchor_fit), ("cell", args.anchor_cell), ("sigma", args.anchor_sigma), ("lam", args.anchor_lambda), ("reject", args.anchor_reject),
+                              ("min_depth", args.min_depth), ("max_depth", args.max_depth)) if v is not None}
+    opts["field"] = not args.anchor_no_field
+    return opts
+
+
+def load_anchor(path, unit):
+    """float32 (H,W) metres: a .npy array as it is, a 16-bit greyscale PNG in steps of ``unit`` metres (one float64 product per pixel, rounded once)"""
+    import numpy as np
+    from . import viz
+    if os.path.splitext(path)[1].lower() == ".npy":
+        a = np.load(path)
+        if a.ndim == 3 and a.shape[0] == 1:
+            a = a[0]
+        if a.ndim != 2 or a.dtype != np.float32:
+            raise SystemExit(f"md_rdm_amd.predict: {path}: an anchor .npy must be a float32 HxW (or 1xHxW) frame in metres, got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a)
+    try:
+        steps = viz.read_png16(path)
+    except ValueError as e:
+        raise SystemExit("md_rdm_amd.predict: %s" % e)
+    return (steps.astype(np.float64) * unit).astype(np.float32)
+
+
 def view_jobs(args):
     """[(file suffix, (3,4) pose)] of the views asked for"""
     import numpy as np
@@ -299,6 +377,7 @@ def main(argv=None):
     check_refine_args(args)
     check_mesh_args(args)
     check_view_args(args)
+    check_anchor_args(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -352,9 +431,17 @@ def main(argv=None):
             region = (480, 640)
         if args.metric:
             frame = batch.shape[1:3] if args.native else region if args.full_res else (128, 128)
+            anchored = {}
+            if args.anchors is not None:
+                frames = [load_anchor(p, args.anchor_unit or 1e-3) for p in args.anchors[i:j]]
+                for p, a in zip(args.anchors[i:j], frames):
+                    if a.shape != tuple(frame):
+                        raise SystemExit("md_rdm_amd.predict: %s: the anchors are %dx%d, the saved frame is %dx%d" % ((p,) + a.shape + tuple(frame)))
+                anchored = dict(anchors=torch.from_numpy(np.stack(frames)).to(dev), anchor=anchor_options(args))
             planes = model.predict_metric(x, frame, view=nyu.test_view(frame) if args.native else None, flip=args.flip, sid=args.sid or "nyu",
                                           offset=args.sid_offset or 0.0, unit=args.depth_unit or 1e-3, outside=args.outside or "zero",
-                                          want=("f32", "u16") if args.png16 else ("f32",), refine=refine_options(args), guide=rgb if args.refine else None)
+                                          want=("f32", "u16") if args.png16 else ("f32",), refine=refine_options(args), guide=rgb if args.refine else None,
+                                          **anchored)
             maps = planes["f32"].unsqueeze(1)
             steps = planes["u16"].cpu().numpy() if args.png16 else None
             views = view_jobs(args)

@@ -85,6 +85,59 @@ def write_png(path, array):
         fh.write(data)
 
 
+def read_png16(path):
+    """16-bit greyscale PNG (colour type 0, not interlaced: what ``write_png16`` and depth sensors' tools write) -> (H,W) uint16.  Standard
+    library only; every scan-line filter of the format (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) is undone."""
+    import numpy as np
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("read_png16: %s is not a PNG file" % path)
+    at, head, idat = 8, None, []
+    while at + 8 <= len(data):
+        n, kind = struct.unpack(">I4s", data[at:at + 8])
+        body = data[at + 8:at + 8 + n]
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+        at += 12 + n
+    if head is None or head[2:] != (16, 0, 0, 0, 0):
+        raise ValueError("read_png16: %s is not a 16-bit greyscale, non-interlaced PNG (IHDR %r)" % (path, head))
+    w, h = head[0], head[1]
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), dtype=np.uint8)
+    if raw.size != h * (1 + 2 * w):
+        raise ValueError("read_png16: %s holds %d bytes of image data, %d expected" % (path, raw.size, h * (1 + 2 * w)))
+    raw = raw.reshape(h, 1 + 2 * w)
+    out = np.zeros((h, 2 * w), dtype=np.uint8)
+    prev = np.zeros(2 * w, dtype=np.int64)
+    for y in range(h):
+        f, line = int(raw[y, 0]), raw[y, 1:].astype(np.int64)
+        if f == 0:
+            cur = line
+        elif f == 2:
+            cur = (line + prev) & 255
+        elif f == 1:                                                 # Sub: the byte two to the left, i.e. a running sum per byte lane
+            cur = (np.cumsum(line.reshape(w, 2), axis=0) & 255).reshape(-1)
+        elif f in (3, 4):
+            cur = np.zeros(2 * w, dtype=np.int64)
+            for i in range(2 * w):
+                a, b, c = (int(cur[i - 2]), int(prev[i]), int(prev[i - 2])) if i >= 2 else (0, int(prev[i]), 0)
+                if f == 3:
+                    pred = (a + b) >> 1
+                else:
+                    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+                    pred = a if pa <= pb and pa <= pc else b if pb <= pc else c
+                cur[i] = (int(line[i]) + pred) & 255
+        else:
+            raise ValueError("read_png16: %s: scan line %d has the unknown filter %d" % (path, y, f))
+        out[y] = cur
+        prev = cur
+    return out.view(">u2").astype(np.uint16).reshape(h, w)
+
+
 def write_png16(path, array):
     """(H,W) uint16 (numpy array or tensor, host or device) -> 16-bit greyscale PNG (colour type 0, big-endian samples), every scan line with
     filter 0: the interchange format of depth maps (``depth.metric_frames``' "u16" plane: steps of ``unit`` metres, 0 = no measurement).
