@@ -4,6 +4,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from . import _lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
@@ -29,10 +31,16 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def header_deps(bench=False):
+    """The headers every object depends on: csrc/*.h and the public headers of _lib.HEADERS (the bench header only for the bench objects)."""
+    public = [h for h in _lib.HEADERS if bench or h != _lib.BENCH_HEADER]
+    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", h) for h in public]
+
+
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", f) for f in ("rdm_hip.h", "rdm_viz.h", "rdm_eval.h", "rdm_eval_view.h", "rdm_optim.h", "rdm_ema.h", "rdm_depth.h", "rdm_cloud.h", "rdm_refine.h", "rdm_mesh.h", "rdm_warp.h", "rdm_anchor.h")]
+    headers = header_deps()
     jobs = []
     for src in sources():
         obj = os.path.join(OBJ, src[:-4] + ".o")
@@ -65,7 +73,7 @@ def build(force=False, verbose=True):
     for src in bsrcs:
         obj = os.path.join(OBJ, "bench_" + src[:-4] + ".o")
         bobjs.append(obj)
-        if force or _stale(obj, [os.path.join(BENCH_SRC, src)] + headers + [os.path.join(HERE, "..", "include", "rdm_bench.h")]):
+        if force or _stale(obj, [os.path.join(BENCH_SRC, src)] + header_deps(bench=True)):
             r = subprocess.run([hipcc] + FLAGS + ["-c", os.path.join(BENCH_SRC, src), "-o", obj], capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError(f"hipcc failed on bench/{src}:\n{r.stderr}")

@@ -1,6 +1,5 @@
-"""C-ABI boundary: every symbol include/rdm_hip.h declares is exported and bound; argument errors
-come back as status codes + messages (no aborts); the product never imports the oracle.  CPU only
-(no compute calls)."""
+"""C-ABI boundary: argument errors come back as status codes + messages (no aborts); the product never imports the oracle (that every
+symbol a header declares is exported and bound with the header's types is tests/test_abi_cpu.py).  CPU only (no compute calls)."""
 import ctypes as C
 import os
 import re
@@ -19,17 +18,6 @@ def L():
     return _lib.lib()
 
 
-def test_header_symbols_exported_and_bound(L):
-    from md_rdm_amd import _lib
-    hdr = open(HEADER).read()
-    declared = set(re.findall(r"\b(rdm_[a-z0-9_]+)\s*\(", hdr))
-    assert declared, "no declarations found"
-    bound = set(_lib.exported_symbols())
-    assert declared == bound, (declared - bound, bound - declared)
-    for name in declared:
-        assert hasattr(L, name)
-
-
 def test_python_option_names_mirror_the_header_enum():
     """_lib.NET_OPT_* (what RDM_Net.py passes to rdm_net_set_option) == rdm_net_option, names and values."""
     from md_rdm_amd import _lib
@@ -39,16 +27,11 @@ def test_python_option_names_mirror_the_header_enum():
     assert declared == {n: getattr(_lib, n) for n in dir(_lib) if n.startswith("NET_OPT_")}
 
 
-def test_bench_library_is_separate_from_the_product(L):
-    """The measurement kernels live in librdm_bench.so (include/rdm_bench.h): declared == bound == exported THERE, and the product
-    library exports none of them."""
+def test_bench_library_is_separate_from_the_product():
+    """The measurement kernels live in librdm_bench.so (include/rdm_bench.h) and rdm_hip.h names none of them; that they are declared == bound ==
+    exported THERE, and that the product library exports none of them, is test_abi_cpu.py's check of every header."""
     from md_rdm_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "rdm_bench.h")).read()
-    declared = set(re.findall(r"\b(rdm_microbench_[a-z0-9_]+)\s*\(", hdr))
-    assert declared and declared == set(_lib.bench_symbols())
-    B = _lib.bench_lib()
-    for name in declared:
-        assert hasattr(B, name) and not hasattr(L, name), name
+    assert all(name.startswith("rdm_microbench_") for name in _lib.symbols(_lib.BENCH_HEADER))
     assert "microbench" not in open(HEADER).read()
 
 

@@ -3,7 +3,6 @@
 command-line flags, and the C-ABI boundary of include/rdm_depth.h (declared == bound == exported, not in rdm_hip.h)."""
 import math
 import os
-import re
 import struct
 import zlib
 
@@ -15,7 +14,6 @@ import depthframe_ref as dref
 from conftest import GOLDEN, ROOT
 from md_rdm_amd import filler
 
-HEADER = os.path.join(ROOT, "include", "rdm_depth.h")
 NAMES = ("nyu", "kitti", "floorplan3d", "Structured3D")
 
 
@@ -199,16 +197,7 @@ def test_host_tensors_are_refused():
 
 # ---- the C ABI of include/rdm_depth.h -------------------------------------------------------------------------------------------------------
 def test_header_symbols_exported_and_bound():
-    from md_rdm_amd import _lib, build
-    build.build(verbose=False)
-    L = _lib.lib()
-    declared = set(re.findall(r"\b(rdm_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)))
-    assert declared == {"rdm_depth_frames"} == set(_lib.depth_symbols())
-    exported = set(re.findall(r"\bT (rdm_\w+)", os.popen("nm -D --defined-only %s" % _lib.LIB_PATH).read()))
-    assert "rdm_depth_frames" in exported and hasattr(L, "rdm_depth_frames")
-    for other in (_lib.exported_symbols(), _lib.viz_symbols(), _lib.eval_symbols(), _lib.eval_view_symbols(), _lib.optim_symbols(), _lib.bench_symbols()):
-        assert "rdm_depth_frames" not in other
+    from md_rdm_amd import _lib
+    assert set(_lib.symbols("rdm_depth.h")) == {"rdm_depth_frames"}      # declared == bound == exported, with the header's types: test_abi_cpu.py
     hip_h = open(os.path.join(ROOT, "include", "rdm_hip.h")).read()
     assert "rdm_depth_frames" not in hip_h and "rdm_depth.h" not in hip_h
-    assert "rdm_depth.h" in open(os.path.join(ROOT, "md_rdm_amd", "build.py")).read()                 # a dependency of every object
-    assert len(_lib._DEPTH_SIGNATURES["rdm_depth_frames"][1]) == 16

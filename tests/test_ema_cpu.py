@@ -3,7 +3,6 @@
 no CPU path for the update itself), the new flags of the three commands, and from_lightning(ema=True) on a checkpoint without averaged weights."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -56,20 +55,14 @@ def test_decay_schedule():
 
 # ---- the C ABI of include/rdm_ema.h ----------------------------------------------------------------------------------------------------------
 def test_header_symbols_exported_and_bound():
-    _lib, L = lib()
-    text = open(HEADER).read()
-    declared = set(re.findall(r"\b(rdm_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", text, flags=re.S)))
-    assert declared == NAMES == set(_lib.ema_symbols())
-    exported = set(re.findall(r"\bT (rdm_\w+)", os.popen("nm -D --defined-only %s" % _lib.LIB_PATH).read()))
+    from md_rdm_amd import _lib
+    assert set(_lib.symbols("rdm_ema.h")) == NAMES          # declared == bound == exported, with the header's types: test_abi_cpu.py
     hip_h = open(os.path.join(ROOT, "include", "rdm_hip.h")).read()
-    for name in declared:
-        assert name in exported and hasattr(L, name)
-        assert name not in _lib.exported_symbols() and name not in _lib.optim_symbols()
+    for name in NAMES:
         assert name not in hip_h                                                              # rdm_hip.h keeps its declaration set
-    assert '#include "rdm_optim.h"' in text
-    assert "rdm_ema.h" in open(os.path.join(ROOT, "md_rdm_amd", "build.py")).read()          # a dependency of every object
+    assert '#include "rdm_optim.h"' in open(HEADER).read()
     # the clipped step's arguments with ema after exp_avg_sq and ema_decay before the stream
-    clip, ema = _lib._OPTIM_SIGNATURES["rdm_adamw_fused_clip"][1], _lib._EMA_SIGNATURES["rdm_adamw_fused_ema"][1]
+    clip, ema = _lib.HEADERS["rdm_optim.h"]["rdm_adamw_fused_clip"][1], _lib.HEADERS["rdm_ema.h"]["rdm_adamw_fused_ema"][1]
     assert ema == clip[:4] + [_lib.vp] + clip[4:-1] + [_lib.f32, _lib.vp]
 
 

@@ -4,7 +4,6 @@ include/rdm_eval_view.h (declared == bound == exported; every refusal is a statu
 import ctypes as C
 import ctypes.util
 import os
-import re
 
 import numpy as np
 import pytest
@@ -232,20 +231,11 @@ def test_predict_signature_has_flip():
 
 # ---- the C ABI of include/rdm_eval_view.h ---------------------------------------------------------------------------------------------------
 def test_header_symbols_exported_and_bound():
-    from md_rdm_amd import _lib, build
-    build.build(verbose=False)
-    L = _lib.lib()
-    hdr = open(HEADER).read()
-    declared = set(re.findall(r"\b(rdm_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)))
-    assert declared == {"rdm_eval_standard_view_f64"} == set(_lib.eval_view_symbols())
-    exported = set(re.findall(r"\bT (rdm_\w+)", os.popen("nm -D --defined-only %s" % _lib.LIB_PATH).read()))
-    assert declared <= exported and hasattr(L, "rdm_eval_standard_view_f64")
-    for other in (_lib.exported_symbols(), _lib.viz_symbols(), _lib.eval_symbols(), _lib.optim_symbols(), _lib.bench_symbols()):
-        assert "rdm_eval_standard_view_f64" not in other
-    assert '#include "rdm_eval.h"' in hdr
-    old, new = _lib._EVAL_SIGNATURES["rdm_eval_standard_f64"][1], _lib._EVAL_VIEW_SIGNATURES["rdm_eval_standard_view_f64"][1]
+    from md_rdm_amd import _lib
+    assert set(_lib.symbols("rdm_eval_view.h")) == {"rdm_eval_standard_view_f64"}    # declared == bound == exported, with the header's types: test_abi_cpu.py
+    assert '#include "rdm_eval.h"' in open(HEADER).read()
+    old, new = _lib.HEADERS["rdm_eval.h"]["rdm_eval_standard_f64"][1], _lib.HEADERS["rdm_eval_view.h"]["rdm_eval_standard_view_f64"][1]
     assert len(new) == 16 and new[:10] == old[:10] and new[11:] == old[10:]          # the same arguments plus the view, after the crop
-    assert "rdm_eval_view.h" in open(os.path.join(ROOT, "md_rdm_amd", "build.py")).read()        # a dependency of every object
 
 
 def test_view_refusals_are_status_codes():

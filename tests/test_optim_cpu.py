@@ -21,20 +21,15 @@ def lib():
 
 # ---- the C ABI of include/rdm_optim.h --------------------------------------------------------------------------------------------------------
 def test_header_symbols_exported_and_bound():
-    _lib, L = lib()
+    from md_rdm_amd import _lib
     text = open(HEADER).read()
-    declared = set(re.findall(r"\b(rdm_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", text, flags=re.S)))
-    assert declared == NAMES == set(_lib.optim_symbols())
-    exported = set(re.findall(r"\bT (rdm_\w+)", os.popen("nm -D --defined-only %s" % _lib.LIB_PATH).read()))
+    assert set(_lib.symbols("rdm_optim.h")) == NAMES        # declared == bound == exported, with the header's types: test_abi_cpu.py
     hip_h = open(os.path.join(ROOT, "include", "rdm_hip.h")).read()
-    for name in declared:
-        assert name in exported and hasattr(L, name)
-        assert name not in _lib.exported_symbols() and name not in _lib.viz_symbols() and name not in _lib.eval_symbols() and name not in _lib.bench_symbols()
+    for name in NAMES:
         assert name not in hip_h                                                                # rdm_hip.h keeps its declaration set
     assert '#include "rdm_hip.h"' in text
-    assert "rdm_optim.h" in open(os.path.join(ROOT, "md_rdm_amd", "build.py")).read()           # a dependency of every object
     # the clipped step takes rdm_adamw_fused's arguments, then sumsq, n_slots, max_norm, coef_out - and the stream stays last
-    plain, clip = _lib._SIGNATURES["rdm_adamw_fused"][1], _lib._OPTIM_SIGNATURES["rdm_adamw_fused_clip"][1]
+    plain, clip = _lib.HEADERS["rdm_hip.h"]["rdm_adamw_fused"][1], _lib.HEADERS["rdm_optim.h"]["rdm_adamw_fused_clip"][1]
     assert clip[:len(plain) - 1] == plain[:-1] and clip[len(plain) - 1:] == [_lib.vp, _lib.i32, _lib.f32, _lib.vp, _lib.vp]
     for macro, value in (("RDM_GRAD_ACC_COPY", _lib.GRAD_ACC_COPY), ("RDM_GRAD_ACC_ADD", _lib.GRAD_ACC_ADD), ("RDM_CLIP_MAX_SLOTS", _lib.CLIP_MAX_SLOTS)):
         assert int(re.search(r"#define %s (\d+)" % macro, text).group(1)) == value

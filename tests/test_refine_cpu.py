@@ -4,7 +4,6 @@ in rdm_hip.h; every bad argument a status code with a message, before any device
 import ctypes as C
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +13,6 @@ import refine_ref as rref
 from conftest import ROOT
 from md_rdm_amd import filler
 
-HEADER = os.path.join(ROOT, "include", "rdm_refine.h")
 INF = math.inf
 
 
@@ -166,19 +164,11 @@ def L():
     return _lib.lib()
 
 
-def test_header_symbols_exported_and_bound(L):
+def test_header_symbols_exported_and_bound():
     from md_rdm_amd import _lib
-    declared = set(re.findall(r"\b(rdm_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)))
-    assert declared == {"rdm_depth_refine"} == set(_lib.refine_symbols())
-    exported = set(re.findall(r"\bT (rdm_\w+)", os.popen("nm -D --defined-only %s" % _lib.LIB_PATH).read()))
-    assert "rdm_depth_refine" in exported and hasattr(L, "rdm_depth_refine")
-    for other in (_lib.exported_symbols(), _lib.viz_symbols(), _lib.eval_symbols(), _lib.eval_view_symbols(), _lib.optim_symbols(), _lib.ema_symbols(), _lib.depth_symbols(),
-                  _lib.cloud_symbols(), _lib.bench_symbols()):
-        assert "rdm_depth_refine" not in other
+    assert set(_lib.symbols("rdm_refine.h")) == {"rdm_depth_refine"}     # declared == bound == exported, with the header's types: test_abi_cpu.py
     hip_h = open(os.path.join(ROOT, "include", "rdm_hip.h")).read()
     assert "rdm_depth_refine" not in hip_h and "rdm_refine.h" not in hip_h
-    assert "rdm_refine.h" in open(os.path.join(ROOT, "md_rdm_amd", "build.py")).read()                # a dependency of every object
-    assert len(_lib._REFINE_SIGNATURES["rdm_depth_refine"][1]) == 14
 
 
 def test_bad_arguments_are_status_codes_before_any_device_call(L):

@@ -7,18 +7,9 @@ import re
 
 import conftest
 import test_gpu_streams as T
+from abi_header import stream_taking_declarations
 
 HEADER = os.path.join(conftest.ROOT, "include", "rdm_hip.h")
-
-
-def stream_taking_declarations(text):
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
-    names = []
-    for m in re.finditer(r"\b(rdm_\w+)\s*\(([^;{}()]*)\)\s*;", text):
-        if re.search(r"\brdm_stream_t\b", m.group(2)):
-            names.append(m.group(1))
-    return names
 
 
 def test_the_parser_sees_the_header():
