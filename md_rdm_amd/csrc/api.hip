@@ -51,6 +51,30 @@ static int geom_from_desc(const rdm_conv_desc* d, ConvGeom* g) {
   *g = ConvGeom{d->batch, d->in_h, d->in_w, ho, wo, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_h, d->pad_w, 1};
   return 0;
 }
+
+// FwdArgs of the convolution `d` describes (g.dir > 0), or of its input gradient (g = the gathering geometry, dir < 0: the two sides swap roles and
+// `out_ld` is the gradient's pixel stride).  Every entry point sets its own extras (prologue, statistics, mask, split) behind it.
+static FwdArgs fwd_args_from_desc(const rdm_conv_desc* d, const ConvGeom& g, const float* A, const float* w, float* out, int out_ld) {
+  const bool fwd = g.dir > 0;
+  FwdArgs a{};
+  a.g = g; a.A = A; a.lda = fwd ? d->in_ld : d->out_ld; a.C = fwd ? d->in_c : d->out_c;
+  a.Wt = w; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
+  a.out = out; a.ldc = out_ld; a.M = g.B * g.Ho * g.Wo; a.N = fwd ? d->out_c : d->in_c;
+  return a;
+}
+static WgradArgs wgrad_args_from_desc(const rdm_conv_desc* d, const ConvGeom& g, const float* dy, const float* x, const float* bn_scale, const float* bn_shift,
+                                      float* dw, int split_k) {
+  WgradArgs a{};
+  a.g = g; a.G = dy; a.ldg = d->out_ld; a.N = d->out_c;
+  a.Xs = x; a.ldx = d->in_ld; a.C = d->in_c; a.x_scale = bn_scale; a.x_shift = bn_shift;
+  a.dW = dw; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
+  a.split_k = split_k;
+  return a;
+}
+// the views (plan_views.h) are shared with the launchers that WRITE these arrays; the C ABI hands the ones an entry point only reads over as const
+template <typename T> static T* rw(const T* p) { return const_cast<T*>(p); }
+static BnParams bwd_params(const float* gamma) { return BnParams(gamma, nullptr, nullptr, nullptr, nullptr); }                         // backward reads gamma ...
+static BnAffine bwd_saved(const float* mean, const float* rstd) { return BnAffine(nullptr, nullptr, rw(mean), rw(rstd)); }      // ... and what forward saved
 }  // namespace rdm
 
 using namespace rdm;
@@ -136,10 +160,8 @@ int rdm_conv2d_fwd_ex(const rdm_conv_desc* d, const float* x, const float* w, co
   RDM_CHECK_ARG((bn_scale == nullptr) == (bn_shift == nullptr), "conv2d_fwd: bn_scale and bn_shift go together");
   RDM_CHECK_ARG((stat_sum == nullptr) == (stat_sq == nullptr), "conv2d_fwd: stat_sum and stat_sq go together");
   RDM_CHECK_ARG(!(stat_sum && bias), "conv2d_fwd: statistics epilogue and bias are mutually exclusive");
-  FwdArgs a{};
-  a.g = g; a.A = x; a.lda = d->in_ld; a.C = d->in_c; a.a_scale = bn_scale; a.a_shift = bn_shift;
-  a.Wt = w; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.out = y; a.ldc = d->out_ld; a.M = g.B * g.Ho * g.Wo; a.N = d->out_c; a.bias = bias;
+  FwdArgs a = fwd_args_from_desc(d, g, x, w, y, d->out_ld);
+  a.a_scale = bn_scale; a.a_shift = bn_shift; a.bias = bias;
   a.stat0 = stat_sum; a.stat1 = stat_sq;
   a.split_k = split_k;
   rc = launch_conv_fwd(a, false, stat_sum ? EPI_STORE_STATS : EPI_STORE, stream);
@@ -154,11 +176,8 @@ int rdm_conv2d_fwd_bnsums(const rdm_conv_desc* d, const float* x, const float* w
   if (rc) return rc;
   RDM_CHECK_ARG(x && w && y && bn_sum && bn_sumsq && bn_gamma && bn_beta && bn_count >= 1, "conv2d_fwd_bnsums: NULL operand");
   RDM_CHECK_ARG((stat_sum == nullptr) == (stat_sq == nullptr), "conv2d_fwd_bnsums: stat_sum and stat_sq go together");
-  FwdArgs a{};
-  a.g = g; a.A = x; a.lda = d->in_ld; a.C = d->in_c;
+  FwdArgs a = fwd_args_from_desc(d, g, x, w, y, d->out_ld);
   a.a_sum = bn_sum; a.a_sq = bn_sumsq; a.a_gamma = bn_gamma; a.a_beta = bn_beta; a.a_count = bn_count;
-  a.Wt = w; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.out = y; a.ldc = d->out_ld; a.M = g.B * g.Ho * g.Wo; a.N = d->out_c;
   a.stat0 = stat_sum; a.stat1 = stat_sq;
   a.split_k = split_k;
   rc = launch_conv_fwd(a, false, stat_sum ? EPI_STORE_STATS : EPI_STORE, stream);
@@ -175,11 +194,8 @@ int rdm_conv3x3_fwd_bnsums_acc(const rdm_conv_desc* d, const float* x, const flo
   RDM_CHECK_ARG(x && w && y && bn_sum && bn_sumsq && bn_gamma && bn_beta && bn_count >= 1 && stat_sum && stat_sq && tile_tickets, "conv3x3_fwd_bnsums_acc: NULL operand");
   RDM_CHECK_ARG(d->kh == 3 && d->kw == 3 && d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 1 && d->pad_w == 1 && d->out_c <= 48 && ((uintptr_t)tile_tickets & 3) == 0,
                 "conv3x3_fwd_bnsums_acc: a 3x3 / stride 1 / pad 1 convolution with <= 48 outputs");
-  FwdArgs a{};
-  a.g = g; a.A = x; a.lda = d->in_ld; a.C = d->in_c;
+  FwdArgs a = fwd_args_from_desc(d, g, x, w, y, d->out_ld);
   a.a_sum = bn_sum; a.a_sq = bn_sumsq; a.a_gamma = bn_gamma; a.a_beta = bn_beta; a.a_count = bn_count;
-  a.Wt = w; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.out = y; a.ldc = d->out_ld; a.M = g.B * g.Ho * g.Wo; a.N = d->out_c;
   a.stat0 = stat_sum; a.stat1 = stat_sq;
   a.split_k = split_k; a.accumulate = 1; a.tickets = tile_tickets;
   rc = launch_conv_fwd(a, false, EPI_STORE, stream);
@@ -203,10 +219,7 @@ int rdm_conv2d_dgrad_ex(const rdm_conv_desc* d, const float* dy, const float* w,
   RDM_CHECK_ARG(!mask_x || (mask_scale && mask_shift && stat_a && stat_b), "conv2d_dgrad: mask needs scale, shift and both statistics");
   // the gradient wrt the input lives on the input grid; gather from the output grid
   ConvGeom gd{d->batch, g.Ho, g.Wo, d->in_h, d->in_w, d->kh, d->kw, 1, 1, d->pad_h, d->pad_w, -1};
-  FwdArgs a{};
-  a.g = gd; a.A = dy; a.lda = d->out_ld; a.C = d->out_c;
-  a.Wt = w; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.out = dx; a.ldc = dx_ld; a.M = d->batch * d->in_h * d->in_w; a.N = d->in_c;
+  FwdArgs a = fwd_args_from_desc(d, gd, dy, w, dx, dx_ld);
   a.X = mask_x; a.ldx = mask_ld; a.x_scale = mask_scale; a.x_shift = mask_shift; a.stat0 = stat_a; a.stat1 = stat_b;
   a.split_k = split_k;
   rc = launch_conv_fwd(a, true, mask_x ? EPI_MASK_STATS : EPI_STORE, stream);
@@ -226,12 +239,7 @@ int rdm_conv2d_wgrad_ex(const rdm_conv_desc* d, const float* dy, const float* x,
   if (rc) return rc;
   RDM_CHECK_ARG(dy && x && dw, "conv2d_wgrad: NULL operand");
   RDM_CHECK_ARG((bn_scale == nullptr) == (bn_shift == nullptr), "conv2d_wgrad: bn_scale and bn_shift go together");
-  WgradArgs a{};
-  a.g = g; a.G = dy; a.ldg = d->out_ld; a.N = d->out_c;
-  a.Xs = x; a.ldx = d->in_ld; a.C = d->in_c; a.x_scale = bn_scale; a.x_shift = bn_shift;
-  a.dW = dw; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.split_k = split_k;
-  return launch_conv_wgrad(a, stream);
+  return launch_conv_wgrad(wgrad_args_from_desc(d, g, dy, x, bn_scale, bn_shift, dw, split_k), stream);
 }
 
 size_t rdm_conv3x3_dgrad_x3_workspace_bytes(int32_t in_c) { return in_c > 0 && in_c % 16 == 0 ? xs_dgrad3x3_workspace_bytes(in_c) : 0; }
@@ -246,10 +254,7 @@ int rdm_conv3x3_dgrad_x3(const rdm_conv_desc* d, const float* dy, const float* w
   RDM_CHECK_ARG(products == 0 || products == 1 || products == 3, "conv3x3_dgrad_x3: products (%d) must be 0 / 3 (split precision) or 1 (bf16 operands)", (int)products);
   RDM_CHECK_ARG(!mask_x || (mask_scale && mask_shift && stat_a && stat_b), "conv3x3_dgrad_x3: mask needs scale, shift and both statistics");
   ConvGeom gd{d->batch, g.Ho, g.Wo, d->in_h, d->in_w, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_h, d->pad_w, -1};
-  FwdArgs a{};
-  a.g = gd; a.A = dy; a.lda = d->out_ld; a.C = d->out_c;
-  a.Wt = w; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.out = dx; a.ldc = dx_ld; a.M = d->batch * d->in_h * d->in_w; a.N = d->in_c;
+  FwdArgs a = fwd_args_from_desc(d, gd, dy, w, dx, dx_ld);
   a.X = mask_x; a.ldx = mask_ld; a.x_scale = mask_scale; a.x_shift = mask_shift; a.stat0 = stat_a; a.stat1 = stat_b;
   if (!xs_dgrad3x3_supported(a)) { set_error("conv3x3_dgrad_x3: no split-precision kernel for this convolution (3x3 / stride 1 / pad 1, out_c = 48, in_c a multiple of 48, rows <= ~330 pixels)"); return RDM_ERR_UNSUPPORTED; }
   return launch_xs_dgrad3x3(a, mask_x ? EPI_MASK_STATS : EPI_STORE, workspace, workspace_bytes, stream, products == 1 ? 1 : 3);
@@ -265,10 +270,8 @@ int rdm_conv1x1_fwd_x6(const rdm_conv_desc* d, const float* x, const float* w, c
   RDM_CHECK_ARG(x && w && y, "conv1x1_fwd_x6: NULL operand");
   RDM_CHECK_ARG(products == 0 || products == 1 || products == 6, "conv1x1_fwd_x6: products (%d) must be 0 / 6 (three-way split) or 1 (bf16 operands)", (int)products);
   RDM_CHECK_ARG((stat_sum == nullptr) == (stat_sq == nullptr), "conv1x1_fwd_x6: both statistics or none");
-  FwdArgs a{};
-  a.g = g; a.A = x; a.lda = d->in_ld; a.C = d->in_c; a.a_scale = bn_scale; a.a_shift = bn_shift;
-  a.Wt = w; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.out = y; a.ldc = d->out_ld; a.M = d->batch * g.Ho * g.Wo; a.N = d->out_c;
+  FwdArgs a = fwd_args_from_desc(d, g, x, w, y, d->out_ld);
+  a.a_scale = bn_scale; a.a_shift = bn_shift;
   a.stat0 = stat_sum; a.stat1 = stat_sq;
   if (!xs_fwd1x1_supported(a)) { set_error("conv1x1_fwd_x6: no split-precision kernel for this convolution (1x1 / stride 1, out_c a multiple of 16, in_c of 4)"); return RDM_ERR_UNSUPPORTED; }
   return launch_xs_fwd1x1(a, stat_sum ? EPI_STORE_STATS : EPI_STORE, workspace, workspace_bytes, stream, products == 1 ? 1 : 6);
@@ -290,10 +293,7 @@ int rdm_conv1x1_dgrad_x3(const rdm_conv_desc* d, const float* dy, const float* w
   RDM_CHECK_ARG(!dy_rows || products != 1, "conv1x1_dgrad_x3: split rows are an operand of the split arithmetic (products 0 / 3)");
   RDM_CHECK_ARG(!mask_x || (mask_scale && mask_shift && stat_a && stat_b), "conv1x1_dgrad_x3: mask needs scale, shift and both statistics");
   ConvGeom gd{d->batch, g.Ho, g.Wo, d->in_h, d->in_w, d->kh, d->kw, d->stride_h, d->stride_w, d->pad_h, d->pad_w, -1};
-  FwdArgs a{};
-  a.g = gd; a.A = dy; a.lda = d->out_ld; a.C = d->out_c;
-  a.Wt = w; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.out = dx; a.ldc = dx_ld; a.M = d->batch * d->in_h * d->in_w; a.N = d->in_c;
+  FwdArgs a = fwd_args_from_desc(d, gd, dy, w, dx, dx_ld);
   a.X = mask_x; a.ldx = mask_ld; a.x_scale = mask_scale; a.x_shift = mask_shift; a.stat0 = stat_a; a.stat1 = stat_b;
   a.a_split = dy_rows;
   a.acc_scaled = acc_scaled;
@@ -315,11 +315,7 @@ int rdm_conv2d_wgrad_x3(const rdm_conv_desc* d, const float* dy, const float* x,
   if (rc) return rc;
   RDM_CHECK_ARG(dy && x && dw, "conv2d_wgrad_x3: NULL operand");
   RDM_CHECK_ARG((bn_scale == nullptr) == (bn_shift == nullptr), "conv2d_wgrad_x3: bn_scale and bn_shift go together");
-  WgradArgs a{};
-  a.g = g; a.G = dy; a.ldg = d->out_ld; a.N = d->out_c;
-  a.Xs = x; a.ldx = d->in_ld; a.C = d->in_c; a.x_scale = bn_scale; a.x_shift = bn_shift;
-  a.dW = dw; a.wtap = (long)d->out_c * d->in_c; a.ldw = d->in_c;
-  a.split_k = split_k;
+  WgradArgs a = wgrad_args_from_desc(d, g, dy, x, bn_scale, bn_shift, dw, split_k);
   a.xsplit = products == 1 ? 1 : 3;
   a.g_split = dy_rows; a.x_split = x_rows; a.g_frame = dy_frame;
   if (d->kh == 1 && d->kw == 1) return launch_xs_wgrad1x1(a, stream);
@@ -594,8 +590,8 @@ int rdm_bn_finalize(const double* sum, const double* sumsq, double count, const 
                     int32_t channels, int32_t training, rdm_stream_t stream) {
   RDM_CHECK_ARG(gamma && beta && running_mean && running_var && scale && shift && save_mean && save_rstd && channels > 0, "bn_finalize: NULL argument");
   RDM_CHECK_ARG(!training || (sum && sumsq && count >= 1), "bn_finalize: training mode needs the sums and a positive count");
-  return launch_bn_finalize(sum, sumsq, count, gamma, beta, running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), scale, shift,
-                            save_mean, save_rstd, channels, training, stream);
+  return launch_bn_finalize(StatPair(rw(sum), rw(sumsq)), count, BnParams(gamma, beta, running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked)),
+                            BnAffine(scale, shift, save_mean, save_rstd), channels, training, stream);
 }
 
 int rdm_bn_bwd_reduce(float* dz, int32_t dz_ld, const float* x, int32_t x_ld, const float* scale, const float* shift, int64_t rows,
@@ -615,8 +611,8 @@ int rdm_bn_bwd(float* dx, int32_t dx_ld, const float* dz, int32_t dz_ld, const f
   if (int rc = check_nhwc(x, x_ld, channels, "bn_bwd(x)")) return rc;
   RDM_CHECK_ARG(sum_dz && sum_dz_x && gamma && save_mean && save_rstd && rows > 0 && rows < (1L << 31) && count >= 1, "bn_bwd: bad argument");
   RDM_CHECK_ARG(accumulate >= 0 && accumulate <= 2, "bn_bwd: accumulate (%d) must be 0 (write), 1 (add) or 2 (write as split rows)", (int)accumulate);
-  return launch_bn_bwd_apply(dx, dx_ld, dz, dz_ld, x, x_ld, sum_dz, sum_dz_x, count, gamma, save_mean, save_rstd, dgamma, dbeta, (int)rows, channels,
-                             accumulate == 1, training, stream, false, accumulate == 2);
+  return launch_bn_bwd_apply(dx, dx_ld, dz, dz_ld, x, x_ld, StatPair(rw(sum_dz), rw(sum_dz_x)), count, bwd_params(gamma), bwd_saved(save_mean, save_rstd),
+                             BnGrads(dgamma, dbeta), (int)rows, channels, accumulate == 1, training, stream, false, accumulate == 2);
 }
 
 int rdm_bn_bwd_defer(float* g, int32_t g_ld, const float* x, int32_t x_ld, const double* sum_dz, const double* sum_dz_x, double count,
@@ -628,8 +624,8 @@ int rdm_bn_bwd_defer(float* g, int32_t g_ld, const float* x, int32_t x_ld, const
   RDM_CHECK_ARG(sum_dz && sum_dz_x && gamma && save_mean && save_rstd && b_in && c_in && b_out && c_out && rows > 0 && rows < (1L << 31) && count >= 1,
                 "bn_bwd_defer: bad argument");
   RDM_CHECK_ARG(b_in != b_out && c_in != c_out, "bn_bwd_defer: the running sums are ping-pong buffers (in != out)");
-  return launch_bn_bwd_defer(g, g_ld, x, x_ld, sum_dz, sum_dz_x, count, gamma, save_mean, save_rstd, dgamma, dbeta, b_in, c_in, b_out, c_out, (int)rows,
-                             channels, slice_c0, slice_n, training, stream);
+  return launch_bn_bwd_defer(g, g_ld, x, x_ld, StatPair(rw(sum_dz), rw(sum_dz_x)), count, bwd_params(gamma), bwd_saved(save_mean, save_rstd), BnGrads(dgamma, dbeta),
+                             b_in, c_in, b_out, c_out, (int)rows, channels, slice_c0, slice_n, training, stream);
 }
 
 int rdm_maxpool3s2_fwd(const float* x, float* y, int32_t y_ld, uint8_t* argmax, int32_t batch, int32_t h, int32_t w, int32_t channels,
@@ -685,7 +681,7 @@ int rdm_padavgpool2_bwd(const float* dpooled, const float* x, int32_t x_ld, cons
   int rc = launch_trans_pool_bwd_reduce(dpooled, x, x_ld, scale, shift, batch, h, w, channels, s0, s1, stream);
   if (rc) return rc;
   const double count = (double)batch * (h + 1) * (w + 1);
-  if ((rc = launch_bn_bwd_coeffs(s0, s1, count, gamma, save_mean, save_rstd, cA, cB, cC, dgamma, dbeta, channels, training, stream))) return rc;
+  if ((rc = launch_bn_bwd_coeffs(StatPair(s0, s1), count, bwd_params(gamma), bwd_saved(save_mean, save_rstd), cA, cB, cC, BnGrads(dgamma, dbeta), channels, training, stream))) return rc;
   return launch_trans_pool_bwd_apply(dpooled, x, x_ld, scale, shift, cA, cB, cC, dx, dx_ld, batch, h, w, channels, stream);
 }
 

@@ -1,6 +1,7 @@
 // internal declarations of the bf16 forward kernels (bf16.hip); not part of the C ABI
 #pragma once
 #include <hip/hip_runtime.h>
+#include "plan_views.h"
 namespace rdm {
 
 struct GemmBf16Args {        // out[m][n] = bias[n] + sum_k f(X[m][k]) * W[n][k],  f = relu(x*scale[k]+shift[k]) when scale != NULL
@@ -76,8 +77,7 @@ struct DenseBf16TrainBlock {
   void* Y; float* partial; size_t partial_floats; float* stats; size_t stats_floats;
   double* bsum; double* bsq; double* ysum; double* ysq; float* aff1; float* aff2;     // aff1 [4][ctot] / aff2 [4][cb] f32: scale | shift | mean | rstd
   const void* w1[48]; const void* w3[48];
-  const float* g1[48]; const float* b1[48]; float* rm1[48]; float* rv1[48]; long long* nbt1[48];
-  const float* g2[48]; const float* b2[48]; float* rm2[48]; float* rv2[48]; long long* nbt2[48];
+  BnParams p1[48], p2[48];                 // norm1 / norm2 of each layer
 };
 int dense_block_bf16_train(const DenseBf16TrainBlock& d, hipStream_t s);
 int launch_trans_pool_bf16(const void* X, int ldx, const float* sc, const float* sh, void* P, int B, int H, int W, int C, hipStream_t s);

@@ -122,11 +122,9 @@ __global__ void k_bn_finalize(const double* sum, const double* sq, double count,
   save_rstd[c] = rstd;
 }
 
-int launch_bn_finalize(const double* sum, const double* sq, double count, const float* gamma, const float* beta, float* rm,
-                       float* rv, long long* nbt, float* scale, float* shift, float* save_mean, float* save_rstd, int C,
-                       int training, hipStream_t s) {
-  hipLaunchKernelGGL(k_bn_finalize, dim3(cdiv(C, 256)), dim3(256), 0, s, sum, sq, count, gamma, beta, rm, rv, nbt, scale, shift,
-                     save_mean, save_rstd, C, training, 0.1f, 1e-5f);
+int launch_bn_finalize(StatPair st, double count, BnParams p, BnAffine a, int C, int training, hipStream_t s) {
+  hipLaunchKernelGGL(k_bn_finalize, dim3(cdiv(C, 256)), dim3(256), 0, s, st.sum, st.sq, count, p.gamma, p.beta, p.rm, p.rv, p.nbt, a.scale, a.shift,
+                     a.mean, a.rstd, C, training, 0.1f, 1e-5f);
   RDM_LAUNCH_OK();
   return 0;
 }
@@ -175,8 +173,10 @@ __global__ void k_bn_bwd_coeffs(const double* s0, const double* s1, double count
   }
 }
 
-int launch_bn_bwd_coeffs(const double* s0, const double* s1, double count, const float* gamma, const float* mean, const float* rstd,
-                         float* A, float* Bc, float* Cc, float* dgamma, float* dbeta, int C, int training, hipStream_t s) {
+int launch_bn_bwd_coeffs(StatPair st, double count, BnParams p, BnAffine a, float* A, float* Bc, float* Cc, BnGrads d, int C, int training, hipStream_t s) {
+  const double *s0 = st.sum, *s1 = st.sq;
+  const float *gamma = p.gamma, *mean = a.mean, *rstd = a.rstd;
+  float *dgamma = d.dgamma, *dbeta = d.dbeta;
   hipLaunchKernelGGL(k_bn_bwd_coeffs, dim3(cdiv(C, 256)), dim3(256), 0, s, s0, s1, count, gamma, mean, rstd, A, Bc, Cc, dgamma, dbeta, C, training);
   RDM_LAUNCH_OK();
   return 0;
@@ -241,9 +241,11 @@ __global__ __launch_bounds__(256) void k_bn_bwd_defer(float* __restrict__ G, int
   }
 }
 
-int launch_bn_bwd_defer(float* G, int ldg, const float* x, int ldx, const double* s0, const double* s1, double count, const float* gamma, const float* mean,
-                        const float* rstd, float* dgamma, float* dbeta, const float* b_in, const float* c_in, float* b_out, float* c_out, int M, int C,
-                        int slice_c0, int slice_n, int training, hipStream_t s) {
+int launch_bn_bwd_defer(float* G, int ldg, const float* x, int ldx, StatPair st, double count, BnParams p, BnAffine a, BnGrads d, const float* b_in,
+                        const float* c_in, float* b_out, float* c_out, int M, int C, int slice_c0, int slice_n, int training, hipStream_t s) {
+  const double *s0 = st.sum, *s1 = st.sq;
+  const float *gamma = p.gamma, *mean = a.mean, *rstd = a.rstd;
+  float *dgamma = d.dgamma, *dbeta = d.dbeta;
   RDM_CHECK_ARG(slice_n > 0 && slice_n % 4 == 0 && slice_c0 % 4 == 0 && slice_c0 + slice_n <= C && ldg % 4 == 0 && ldx % 4 == 0 && slice_n <= 4096,
                 "bn_bwd_defer: slice [%d, +%d) of %d channels", slice_c0, slice_n, C);
   const long total = (long)M * (slice_n / 4);
@@ -392,9 +394,11 @@ __global__ __launch_bounds__(256, 8) void k_bn_bwd_apply(float* dst, int ldd, co
   }
 }
 
-int launch_bn_bwd_apply(float* dst, int ldd, const float* dz, int ldz, const float* x, int ldx, const double* s0, const double* s1, double count,
-                        const float* gamma, const float* mean, const float* rstd, float* dgamma, float* dbeta, int M, int C, bool accumulate,
-                        int training, hipStream_t s, bool bf16_rows, bool split_rows) {
+int launch_bn_bwd_apply(float* dst, int ldd, const float* dz, int ldz, const float* x, int ldx, StatPair st, double count, BnParams p, BnAffine a, BnGrads d,
+                        int M, int C, bool accumulate, int training, hipStream_t s, bool bf16_rows, bool split_rows) {
+  const double *s0 = st.sum, *s1 = st.sq;
+  const float *gamma = p.gamma, *mean = a.mean, *rstd = a.rstd;
+  float *dgamma = d.dgamma, *dbeta = d.dbeta;
   const int C4 = C / 4, gx = cdiv(C4, 64);
   RDM_CHECK_ARG(!((bf16_rows || split_rows) && accumulate) && !(bf16_rows && split_rows), "bn_bwd: bf16 / split rows are built for the plain (norm2) form, one at a time");
   const long ez = bf16_rows ? 2 : 4;

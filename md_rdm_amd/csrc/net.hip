@@ -34,9 +34,9 @@ struct TransDef { const char* name; int cin; int cout; };
 const BlockDef kBlocks[4] = {{"encoder.dense_e2", 6, 96, 57}, {"encoder.dense_e3", 12, 192, 29}, {"encoder.dense_e4", 36, 384, 15},
                              {"d_1.dense_layer", 24, 1056, 8}};
 const TransDef kTrans[3] = {{"encoder.trans_e2", 384, 192}, {"encoder.trans_e3", 768, 384}, {"encoder.trans_e4", 2112, 1056}};
+inline int layer_cin(int b, int i) { return kBlocks[b].cin + i * GROWTH; }      // input channels of dense layer i of block b: the block's own + 48 per earlier layer
 
 struct TensorInfo { std::string name; int64_t numel; int is_param; };
-struct BnIdx { int w, b, rm, rv, nbt; };
 struct LayerIdx { BnIdx bn1; int conv1; BnIdx bn2; int conv2; };
 struct Registry {
   std::vector<TensorInfo> t;
@@ -90,7 +90,7 @@ struct Registry {
     const BlockDef& d = kBlocks[bi];
     for (int i = 0; i < d.layers; ++i) {
       const std::string p = std::string(d.name) + ".denselayer" + std::to_string(i + 1);
-      const int c = d.cin + i * GROWTH, cb = d.bn_size * GROWTH;
+      const int c = layer_cin(bi, i), cb = d.bn_size * GROWTH;
       LayerIdx L;
       L.bn1 = add_bn(p + ".norm1", c);
       L.conv1 = add(p + ".conv1.weight", (int64_t)cb * c, 1);
@@ -186,6 +186,9 @@ static hipStream_t shared_side_stream() {
 // 52.6 ms per step); with RDM_NET_OPT_PREPACK and RDM_NET_OPT_DEFER_NORM1 it gains (49.8-50.1 vs 50.4-50.7): the threshold is the kernels' own minimum
 constexpr int XS_LAYOUT_MIN_PIXELS = 1024, XF_LAYOUT_MIN_PIXELS = 8192, XS_WG3_MIN_PIXELS = 8192;
 
+// the plan's events.  EV_DZ / EV_FS / EV_FA are pairs (+ parity of the layer); EV_PKF / EV_PKB: the pre-packed weight images of forward / backward are complete
+enum { EV_GO, EV_DY, EV_DZ, EV_SIDE = EV_DZ + 2, EV_FS, EV_FA = EV_FS + 2, EV_PKF = EV_FA + 2, EV_PKB, EV_COUNT };
+
 struct NetImpl {
   int B, H0, W0, H1, W1;
   BlockGeom bg[4];
@@ -199,28 +202,36 @@ struct NetImpl {
   // weight gradients run on a library-owned side stream, fenced with events against the caller's
   // stream: wgrad of a layer only depends on tensors that are final when its dgrad chain starts
   hipStream_t side = nullptr;
-  hipEvent_t ev_go = nullptr, ev_dy = nullptr, ev_dz[2] = {nullptr, nullptr}, ev_side = nullptr, ev_fs[2] = {nullptr, nullptr}, ev_fa[2] = {nullptr, nullptr};
+  struct Events {              // owns all of the plan's events: they exist together or not at all
+    hipEvent_t e[EV_COUNT] = {};
+    hipEvent_t operator[](int i) const { return e[i]; }
+    int create() {
+      for (hipEvent_t& x : e) {
+        const hipError_t err = hipEventCreateWithFlags(&x, hipEventDisableTiming);
+        if (err == hipSuccess) continue;
+        x = nullptr;
+        destroy();               // the ones created before it
+        set_error("hipEventCreateWithFlags failed: %s (%s:%d)", hipGetErrorString(err), __FILE__, __LINE__);
+        return RDM_ERR_HIP;
+      }
+      return 0;
+    }
+    void destroy() {
+      for (hipEvent_t& x : e)
+        if (x) { (void)hipEventDestroy(x); x = nullptr; }
+    }
+    ~Events() { destroy(); }
+  } ev;
   bool dz_busy[2] = {false, false};
   int ensure_side() {
     if (side) return 0;
-    side = shared_side_stream();
-    if (!side) return RDM_ERR_HIP;
-    RDM_HIP_OK(hipEventCreateWithFlags(&ev_go, hipEventDisableTiming));
-    RDM_HIP_OK(hipEventCreateWithFlags(&ev_dy, hipEventDisableTiming));
-    RDM_HIP_OK(hipEventCreateWithFlags(&ev_dz[0], hipEventDisableTiming));
-    RDM_HIP_OK(hipEventCreateWithFlags(&ev_dz[1], hipEventDisableTiming));
-    RDM_HIP_OK(hipEventCreateWithFlags(&ev_side, hipEventDisableTiming));
-    RDM_HIP_OK(hipEventCreateWithFlags(&ev_pkf, hipEventDisableTiming));
-    RDM_HIP_OK(hipEventCreateWithFlags(&ev_pkb, hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) {
-      RDM_HIP_OK(hipEventCreateWithFlags(&ev_fs[i], hipEventDisableTiming));
-      RDM_HIP_OK(hipEventCreateWithFlags(&ev_fa[i], hipEventDisableTiming));
-    }
+    hipStream_t st = shared_side_stream();
+    if (!st) return RDM_ERR_HIP;
+    if (int rc = ev.create()) return rc;      // nothing is left behind: the next call tries again
+    side = st;                                 // published last: `side` is set <=> every event exists
     return 0;
   }
-  ~NetImpl() {
-    if (side) { hipStreamSynchronize(side); hipEventDestroy(ev_go); hipEventDestroy(ev_dy); hipEventDestroy(ev_dz[0]); hipEventDestroy(ev_dz[1]); hipEventDestroy(ev_side); hipEventDestroy(ev_pkf); hipEventDestroy(ev_pkb); hipEventDestroy(ev_fs[0]); hipEventDestroy(ev_fs[1]); hipEventDestroy(ev_fa[0]); hipEventDestroy(ev_fa[1]); }
-  }
+  ~NetImpl() { if (side) (void)hipStreamSynchronize(side); }      // the events go with `ev`, after this
   // Winograd F(2x2, 3x3) for the 3x3 convs of the blocks with many pixels (wino.hip): transformed weights per layer (formed on the side
   // stream at the start of forward) and one scratch for the per-split partial outputs
   bool wino_fwd[4] = {false, false, false, false}, wino_wg[4] = {false, false, false, false};
@@ -233,7 +244,6 @@ struct NetImpl {
   // dependent chains): 3x3 dgrad / 1x1 dgrad / 1x1 forward images; empty where the block is below the kernels' default pixel thresholds
   std::vector<size_t> xsP3[4], xsP1[4], xfP[4];
   bool pk_fwd_valid = false, pk_bwd_valid = false;
-  hipEvent_t ev_pkf = nullptr, ev_pkb = nullptr;
   int opt_prepack = 1;
   size_t deferBC = 0; int deferLd = 0;      // deferred norm1 backward: [parity 2][B | C][deferLd] running per-channel sums of the block being walked
   std::vector<size_t> winoU[4];
@@ -276,7 +286,7 @@ struct NetImpl {
       bf_act3[b] = b < 2;
       bfl[b].resize(kBlocks[b].layers);
       for (int i = 0; i < kBlocks[b].layers; ++i) {
-        const int cin = kBlocks[b].cin + i * GROWTH;
+        const int cin = layer_cin(b, i);
         bfl[b][i].w1 = w.take<unsigned short>((size_t)cbp * cin);
         bfl[b][i].w3 = w.take<unsigned short>((size_t)9 * GROWTH * cbp);             // either layout: 27 KiB per 32 channels
         bfl[b][i].bn1 = w.take<float>(4 * (size_t)cin);
@@ -315,7 +325,7 @@ struct NetImpl {
     double by = (double)B * 3 * H0 * W0 * 4 + 2.0 * M1 * 160 * 2 + 2.0 * M1 * 96 * 2 + (double)bg[0].M * 96 * 2;
     for (int b = 0; b < 4; ++b)
       for (int i = 0; i < kBlocks[b].layers; ++i)
-        by += (double)bg[b].M * 2 * ((kBlocks[b].cin + i * GROWTH) + 2.0 * bg[b].cb + GROWTH) + 2.0 * ((double)bg[b].cb * (kBlocks[b].cin + i * GROWTH) + 9.0 * GROWTH * bg[b].cb);
+        by += (double)bg[b].M * 2 * (layer_cin(b, i) + 2.0 * bg[b].cb + GROWTH) + 2.0 * ((double)bg[b].cb * layer_cin(b, i) + 9.0 * GROWTH * bg[b].cb);
     for (int t = 0; t < 3; ++t)
       by += (double)bg[t].M * kTrans[t].cin * 2 + 2.0 * bg[t + 1].M * kTrans[t].cin * 2 + (double)bg[t + 1].M * kTrans[t].cout * 2 + 2.0 * kTrans[t].cin * kTrans[t].cout;
     by += (double)bg[3].M * 2208 * 2 + 2.0 * 180 * 2208 + 2.0 * bg[3].M * 180 * 4;
@@ -351,7 +361,7 @@ struct NetImpl {
       for (int i = 0; i < kBlocks[b].layers; ++i) {
         LayerWs& L = lws[b][i];
         L.Y = a.take<float>((size_t)bg[b].M * bg[b].cb);
-        L.bn1 = a.take<float>(4 * (size_t)(kBlocks[b].cin + i * GROWTH));
+        L.bn1 = a.take<float>(4 * (size_t)layer_cin(b, i));
         L.bn2 = a.take<float>(4 * (size_t)bg[b].cb);
         L.w2p = a.take<float>(9 * (size_t)GROWTH * bg[b].cb);
       }
@@ -392,18 +402,18 @@ struct NetImpl {
         xsP3[b].resize(kBlocks[b].layers); xsP1[b].resize(kBlocks[b].layers);
         for (int i = 0; i < kBlocks[b].layers; ++i) {
           xsP3[b][i] = a.take<unsigned char>(xs_dgrad3x3_workspace_bytes(bg[b].cb));
-          xsP1[b][i] = a.take<unsigned char>(xs_dgrad1x1_workspace_bytes(bg[b].cb, kBlocks[b].cin + i * GROWTH));
+          xsP1[b][i] = a.take<unsigned char>(xs_dgrad1x1_workspace_bytes(bg[b].cb, layer_cin(b, i)));
         }
       }
       if (bg[b].M >= XF_LAYOUT_MIN_PIXELS) {
         xfP[b].resize(kBlocks[b].layers);
-        for (int i = 0; i < kBlocks[b].layers; ++i) xfP[b][i] = a.take<unsigned char>(xs_fwd1x1_workspace_bytes(kBlocks[b].cin + i * GROWTH, bg[b].cb));
+        for (int i = 0; i < kBlocks[b].layers; ++i) xfP[b][i] = a.take<unsigned char>(xs_fwd1x1_workspace_bytes(layer_cin(b, i), bg[b].cb));
       }
     }
     {
       size_t xh = 0;                                             // [M][cin] split rows of the widest layer of every block on the split kernels
       for (int b = 0; b < 4; ++b)
-        if (bg[b].M >= XS_LAYOUT_MIN_PIXELS) xh = std::max(xh, (size_t)bg[b].M * (size_t)(kBlocks[b].cin + (kBlocks[b].layers - 1) * GROWTH));
+        if (bg[b].M >= XS_LAYOUT_MIN_PIXELS) xh = std::max(xh, (size_t)bg[b].M * (size_t)layer_cin(b, kBlocks[b].layers - 1));
       xsXh = a.take<float>(xh);
       size_t gf = 0;
       for (int b = 0; b < 4; ++b)
@@ -435,7 +445,7 @@ struct NetImpl {
     for (int b = 0; b < 4; ++b)
       for (int i = 0; i < kBlocks[b].layers; ++i) {
         lws[b][i].bs2 = a.take<double>(2 * (size_t)bg[b].cb);
-        lws[b][i].bs1 = a.take<double>(2 * (size_t)(kBlocks[b].cin + i * GROWTH));
+        lws[b][i].bs1 = a.take<double>(2 * (size_t)layer_cin(b, i));
       }
     for (int t = 0; t < 3; ++t) transBs[t] = a.take<double>(2 * (size_t)kTrans[t].cin);
     bwd_stats_end = a.take<double>(0);
@@ -487,7 +497,7 @@ void resolve_routes(NetImpl& n) {
     const bool dg3_xs = R.xs && xs_dgrad3x3_supported(d3);
     R.layer.assign(layers, LayerRoute{});
     for (int i = 0; i < layers; ++i) {
-      const int cin = kBlocks[b].cin + i * GROWTH;
+      const int cin = layer_cin(b, i);
       FwdArgs f1{}, d1{};
       f1.g = d1.g = geom1x1(n.B, g.H, g.W); f1.M = d1.M = g.M;
       f1.C = cin; f1.N = g.cb;                                 // conv1 forward over all of the layer's input channels
@@ -521,43 +531,118 @@ const BlockRoute& route(NetImpl& n, int b) {
   return n.routes[b];
 }
 
-// norm1 finalisation of layer i restricted to channels [c_lo, c_hi) of the block buffer
-int finalize_norm1(NetImpl& n, int b, int i, int c_lo, int c_hi, bool count_batch, void* ws, void* const* T, int training, hipStream_t s) {
-  const BlockGeom& g = n.bg[b];
-  const LayerIdx& L = reg().layers[b][i];
-  const int cin = kBlocks[b].cin + i * GROWTH;
-  double* bst = at<double>(ws, n.blkstat[b]);
-  float* bn1 = at<float>(ws, n.lws[b][i].bn1);
-  return launch_bn_finalize(bst + c_lo, bst + g.ctot + c_lo, (double)g.M, F(T, L.bn1.w) + c_lo, F(T, L.bn1.b) + c_lo, F(T, L.bn1.rm) + c_lo,
-                            F(T, L.bn1.rv) + c_lo, count_batch ? static_cast<long long*>(T[L.bn1.nbt]) : nullptr, bn1 + c_lo, bn1 + cin + c_lo,
-                            bn1 + 2 * cin + c_lo, bn1 + 3 * cin + c_lo, c_hi - c_lo, training, s);
-}
+// One dense layer (block b, layer i) as the walk sees it - extents, workspace records, tensors - resolved in ONE place (layer_view).  conv1 (1x1)
+// contracts the block-buffer channels [0, cin) into the cb bottleneck channels of Y; conv2 (3x3) writes the 48 channels [cin, cin + 48) behind them.
+struct LayerView {
+  const BlockGeom& g;
+  int B, cin, cb;
+  float *blk, *out, *Y;                 // block buffer = conv1's input range / its 48-channel slice conv2 writes (row stride g.ctot both) / the bottleneck (row stride cb)
+  float *w1, *w2, *w2p;                 // conv1.weight [cb][cin] / conv2.weight as the caller holds it / the [tap][out][in] image the kernels read (== w2 with RDM_NET_OPT_PACKED_3X3)
+  BnAffine bn1, bn2;
+  BnParams p1, p2;
+  BnGrads d1, d2;                       // null slots in forward (Gr == nullptr)
+  StatPair bst, ost, statY, bs1, bs2;   // channel sums of the block buffer (from channel 0) / of the 48-channel slice / of Y / backward sums of norm1, norm2
+};
 
-// conv1 (1x1) of layer i over the input channels [c_lo, c_hi); accumulate => atomically added into a zeroed Y
-int conv1_range(NetImpl& n, int b, int i, int c_lo, int c_hi, bool accumulate, bool fuse, void* ws, void* const* T, hipStream_t s, bool add_out = false,
-                bool raw_bn = false) {
+LayerView layer_view(const NetImpl& n, int b, int i, void* ws, void* const* T, void* const* Gr = nullptr) {
   const BlockGeom& g = n.bg[b];
   const LayerIdx& L = reg().layers[b][i];
   const LayerWs& W = n.lws[b][i];
-  const int cin = kBlocks[b].cin + i * GROWTH;
-  float* bn1 = at<float>(ws, W.bn1);
-  double* sty = at<double>(ws, W.statY);
+  const int cin = layer_cin(b, i), cb = g.cb;
+  float* blk = at<float>(ws, n.blk[b]);
+  const StatPair bst(at<double>(ws, n.blkstat[b]), g.ctot);
+  return LayerView{g, n.B, cin, cb, blk, blk + cin, at<float>(ws, W.Y), F(T, L.conv1), F(T, L.conv2), n.opt_packed3x3 ? F(T, L.conv2) : at<float>(ws, W.w2p),
+                   BnAffine(at<float>(ws, W.bn1), cin), BnAffine(at<float>(ws, W.bn2), cb), BnParams(T, L.bn1), BnParams(T, L.bn2), BnGrads(Gr, L.bn1), BnGrads(Gr, L.bn2),
+                   bst, bst.at(cin), StatPair(at<double>(ws, W.statY), cb), StatPair(at<double>(ws, W.bs1), cin), StatPair(at<double>(ws, W.bs2), cb)};
+}
+
+// The operand descriptions of the layer's two convolutions, one function per struct type; a launch site adds what is particular to it (epilogue
+// flags, accumulate, tickets, the encodings of its LayerRoute, scratch buffers).
+// conv1 over the input channels [c_lo, c_hi): forward, input gradient (dY -> dX), weight gradient
+FwdArgs conv1_fwd_args(const LayerView& V, int c_lo, int c_hi) {
   FwdArgs a{};
-  a.g = geom1x1(n.B, g.H, g.W);
-  a.A = at<float>(ws, n.blk[b]) + c_lo; a.lda = g.ctot; a.C = c_hi - c_lo; a.a_scale = bn1 + c_lo; a.a_shift = bn1 + cin + c_lo;
-  a.Wt = F(T, L.conv1) + c_lo; a.wtap = 0; a.ldw = cin;
-  a.out = at<float>(ws, W.Y); a.ldc = g.cb; a.M = g.M; a.N = g.cb;
-  a.stat0 = sty; a.stat1 = sty + g.cb;
+  a.g = geom1x1(V.B, V.g.H, V.g.W);
+  a.A = V.blk + c_lo; a.lda = V.g.ctot; a.C = c_hi - c_lo; a.a_scale = V.bn1.scale + c_lo; a.a_shift = V.bn1.shift + c_lo;
+  a.Wt = V.w1 + c_lo; a.wtap = 0; a.ldw = V.cin;
+  a.out = V.Y; a.ldc = V.cb; a.M = V.g.M; a.N = V.cb;
+  a.stat0 = V.statY.sum; a.stat1 = V.statY.sq;
+  return a;
+}
+FwdArgs conv1_dgrad_args(const LayerView& V, const float* dY, float* dX) {
+  FwdArgs a{};
+  a.g = geom1x1(V.B, V.g.H, V.g.W);
+  a.A = dY; a.lda = V.cb; a.C = V.cb;
+  a.Wt = V.w1; a.wtap = 0; a.ldw = V.cin;
+  a.out = dX; a.ldc = V.cin; a.M = V.g.M; a.N = V.cin;
+  a.stat0 = V.bs1.sum; a.stat1 = V.bs1.sq; a.X = V.blk; a.ldx = V.g.ctot; a.x_scale = V.bn1.scale; a.x_shift = V.bn1.shift;
+  return a;
+}
+WgradArgs conv1_wgrad_args(const LayerView& V, const float* dY, float* dW) {
+  WgradArgs w{};
+  w.g = geom1x1(V.B, V.g.H, V.g.W);
+  w.G = dY; w.ldg = V.cb; w.N = V.cb;
+  w.Xs = V.blk; w.ldx = V.g.ctot; w.C = V.cin; w.x_scale = V.bn1.scale; w.x_shift = V.bn1.shift;
+  w.dW = dW; w.wtap = 0; w.ldw = V.cin;
+  return w;
+}
+// conv2: forward (direct / Winograd), weight gradient of the slice's gradient `go` (direct or split / Winograd), input gradient go -> dZ
+FwdArgs conv2_fwd_args(const LayerView& V) {
+  FwdArgs c{};
+  c.g = geom3x3(V.B, V.g.H, V.g.W, 1);
+  c.A = V.Y; c.lda = V.cb; c.C = V.cb; c.a_scale = V.bn2.scale; c.a_shift = V.bn2.shift;
+  c.Wt = V.w2p; c.wtap = (long)GROWTH * V.cb; c.ldw = V.cb;
+  c.out = V.out; c.ldc = V.g.ctot; c.M = V.g.M; c.N = GROWTH;
+  c.stat0 = V.ost.sum; c.stat1 = V.ost.sq;
+  return c;
+}
+WinoConv conv2_wino_args(const LayerView& V) {
+  WinoConv wv{};
+  wv.A = V.Y; wv.lda = V.cb; wv.C = V.cb; wv.a_scale = V.bn2.scale; wv.a_shift = V.bn2.shift;
+  wv.out = V.out; wv.ldc = V.g.ctot; wv.N = GROWTH; wv.B = V.B; wv.H = V.g.H; wv.W = V.g.W;
+  return wv;
+}
+WgradArgs conv2_wgrad_args(const LayerView& V, const float* go, float* dW) {
+  WgradArgs w{};
+  w.g = geom3x3(V.B, V.g.H, V.g.W, 1);
+  w.G = go; w.ldg = V.g.ctot; w.N = GROWTH; w.Xs = V.Y; w.ldx = V.cb; w.C = V.cb; w.x_scale = V.bn2.scale; w.x_shift = V.bn2.shift;
+  w.dW = dW; w.wtap = (long)GROWTH * V.cb; w.ldw = V.cb;
+  return w;
+}
+WinoWgrad conv2_wino_wgrad_args(const LayerView& V, const float* go, float* dW) {
+  WinoWgrad wv{};
+  wv.G = go; wv.ldg = V.g.ctot; wv.N = GROWTH; wv.A = V.Y; wv.lda = V.cb; wv.C = V.cb; wv.a_scale = V.bn2.scale; wv.a_shift = V.bn2.shift;
+  wv.dW = dW; wv.wtap = (long)GROWTH * V.cb; wv.ldw = V.cb;
+  wv.B = V.B; wv.H = V.g.H; wv.W = V.g.W;
+  return wv;
+}
+FwdArgs conv2_dgrad_args(const LayerView& V, const float* go, float* dZ) {
+  FwdArgs d{};
+  d.g = geom3x3(V.B, V.g.H, V.g.W, -1);
+  d.A = go; d.lda = V.g.ctot; d.C = GROWTH;
+  d.Wt = V.w2p; d.wtap = (long)GROWTH * V.cb; d.ldw = V.cb;
+  d.out = dZ; d.ldc = V.cb; d.M = V.g.M; d.N = V.cb;
+  d.stat0 = V.bs2.sum; d.stat1 = V.bs2.sq; d.X = V.Y; d.ldx = V.cb; d.x_scale = V.bn2.scale; d.x_shift = V.bn2.shift;
+  return d;
+}
+
+// norm1 finalisation of the layer restricted to channels [c_lo, c_hi) of the block buffer
+int finalize_norm1(const LayerView& V, int c_lo, int c_hi, bool count_batch, int training, hipStream_t s) {
+  return launch_bn_finalize(V.bst.at(c_lo), (double)V.g.M, V.p1.at(c_lo, count_batch), V.bn1.at(c_lo), c_hi - c_lo, training, s);
+}
+
+// conv1 (1x1) of layer i over the input channels [c_lo, c_hi); accumulate => atomically added into a zeroed Y
+int conv1_range(NetImpl& n, int b, int i, const LayerView& V, int c_lo, int c_hi, bool accumulate, bool fuse, void* ws, hipStream_t s, bool add_out = false,
+                bool raw_bn = false) {
+  FwdArgs a = conv1_fwd_args(V, c_lo, c_hi);
   a.accumulate = accumulate ? 1 : 0;
   a.add_out = add_out ? 1 : 0;
   if (raw_bn) {          // the consumer forms the BatchNorm affine of its channels from the block's channel sums (no finalisation launch on the chain)
-    double* bst = at<double>(ws, n.blkstat[b]);
     a.a_scale = nullptr; a.a_shift = nullptr;
-    a.a_sum = bst + c_lo; a.a_sq = bst + g.ctot + c_lo; a.a_gamma = F(T, L.bn1.w) + c_lo; a.a_beta = F(T, L.bn1.b) + c_lo; a.a_count = (double)g.M;
+    a.a_sum = V.bst.sum + c_lo; a.a_sq = V.bst.sq + c_lo; a.a_gamma = V.p1.gamma + c_lo; a.a_beta = V.p1.beta + c_lo; a.a_count = (double)V.g.M;
   }
   if (route(n, b).xf && !accumulate && !add_out && !raw_bn) {
-    const bool pk = n.pk_fwd_valid && !n.xfP[b].empty() && c_lo == 0 && c_hi == cin;
-    return launch_xs_fwd1x1(a, fuse ? EPI_STORE_STATS : EPI_STORE, at<unsigned char>(ws, pk ? n.xfP[b][i] : n.xfW), pk ? xs_fwd1x1_workspace_bytes(cin, g.cb) : n.xfWBytes, s,
+    const bool pk = n.pk_fwd_valid && !n.xfP[b].empty() && c_lo == 0 && c_hi == V.cin;
+    return launch_xs_fwd1x1(a, fuse ? EPI_STORE_STATS : EPI_STORE, at<unsigned char>(ws, pk ? n.xfP[b][i] : n.xfW), pk ? xs_fwd1x1_workspace_bytes(V.cin, V.cb) : n.xfWBytes, s,
                             (n.opt_gemm_bf16 & 1) ? 1 : 6, pk);
   }
   const int rc = launch_conv_fwd(a, false, fuse ? EPI_STORE_STATS : EPI_STORE, s);
@@ -566,8 +651,6 @@ int conv1_range(NetImpl& n, int b, int i, int c_lo, int c_hi, bool accumulate, b
 
 int forward_block(NetImpl& n, int b, void* ws, void* const* T, int training, hipStream_t s) {
   const BlockGeom& g = n.bg[b];
-  float* blk = at<float>(ws, n.blk[b]);
-  double* bst = at<double>(ws, n.blkstat[b]);
   const int layers = kBlocks[b].layers;
   // Small-M blocks (dense_e4, decoder) are a strictly serial chain of short kernels that cannot fill the
   // chip.  DenseNet structure to the rescue: conv1 of layer i+1 contracts over ALL earlier channels, and
@@ -578,13 +661,13 @@ int forward_block(NetImpl& n, int b, void* ws, void* const* T, int training, hip
   const bool pipelined = R.pipelined;
   hipStream_t side = n.side;
   int rc;
-  if (b == 0 && n.pk_fwd_valid) RDM_HIP_OK(hipStreamWaitEvent(s, n.ev_pkf, 0));                 // the packed conv1 weights of the split forward kernel
+  if (b == 0 && n.pk_fwd_valid) RDM_HIP_OK(hipStreamWaitEvent(s, n.ev[EV_PKF], 0));                 // the packed conv1 weights of the split forward kernel
   // Few-pixel blocks in training (round 3): the two BatchNorm finalisations of a layer leave the dependent chain - the consuming conv
   // forms (scale, shift) from the channel sums itself (RAW prologue), the running statistics and the coefficients backward needs are written
   // by BATCHED finalisation launches (24 BatchNorms each) - and the 48-channel output slices of ALL layers are zeroed by ONE launch at the start
   // of the block (their K-split 3x3 convs then only add).  Per layer: 6 -> 3 launches on the chain, ~2.9 launches fewer in all.
   const bool raw = R.raw && training;
-  if (raw && (rc = launch_zero_rows(blk + kBlocks[b].cin, g.M, g.ctot - kBlocks[b].cin, g.ctot, s))) return rc;
+  if (raw && (rc = launch_zero_rows(at<float>(ws, n.blk[b]) + kBlocks[b].cin, g.M, g.ctot - kBlocks[b].cin, g.ctot, s))) return rc;
   // RAW mode bookkeeping (running statistics + the coefficients backward reads): nothing in forward waits for it, so it is BATCHED - up to
   // BN_BATCH BatchNorms per launch, enqueued on the caller's stream once their sums are final (the sums stay untouched until the next forward)
   BnBatch batch;
@@ -594,90 +677,72 @@ int forward_block(NetImpl& n, int b, void* ws, void* const* T, int training, hip
     nbatch = 0; batch_maxc = 0;
     return r;
   };
-  auto add_batch = [&](const double* sum, const double* sq, const BnIdx& bn, int c_lo, int c_hi, float* out, int cfull, bool count_batch) -> int {
-    BnBatchEntry& e = batch.e[nbatch++];
-    e.sum = sum + c_lo; e.sq = sq + c_lo; e.gamma = F(T, bn.w) + c_lo; e.beta = F(T, bn.b) + c_lo; e.rm = F(T, bn.rm) + c_lo; e.rv = F(T, bn.rv) + c_lo;
-    e.nbt = count_batch ? static_cast<long long*>(T[bn.nbt]) : nullptr; e.out = out + c_lo; e.count = (double)g.M; e.C = c_hi - c_lo; e.Cout = cfull;
-    batch_maxc = std::max(batch_maxc, c_hi - c_lo);
+  auto add_batch = [&](StatPair st, BnParams p, BnAffine a, int C) -> int {
+    batch.e[nbatch++] = bn_batch_entry(st, (double)g.M, p, a, C);
+    batch_maxc = std::max(batch_maxc, C);
     return nbatch == BN_BATCH ? flush_batch() : 0;
   };
-  if (pipelined) RDM_HIP_OK(hipEventRecord(n.ev_fs[1], s));        // statistics of the block's input channels are final ("layer -1")
+  auto add_norm2 = [&](int j) -> int {
+    const LayerView P = layer_view(n, b, j, ws, T);
+    return add_batch(P.statY, P.p2, P.bn2, g.cb);
+  };
+  if (pipelined) RDM_HIP_OK(hipEventRecord(n.ev[EV_FS + 1], s));        // statistics of the block's input channels are final ("layer -1")
   for (int i = 0; i < layers; ++i) {
-    const LayerIdx& L = reg().layers[b][i];
-    const LayerWs& W = n.lws[b][i];
-    const int cin = kBlocks[b].cin + i * GROWTH;
-    float* Y = at<float>(ws, W.Y);
-    float* bn2 = at<float>(ws, W.bn2);
-    double* sty = at<double>(ws, W.statY);
+    const LayerView V = layer_view(n, b, i, ws, T);
+    const int cin = V.cin, c48 = cin - GROWTH;
+    if (raw && i > 0 && (rc = add_batch(V.bst.at(c48), V.p1.at(c48, false), V.bn1.at(c48), GROWTH))) return rc;   // layer i's newest 48 channels (sums final since layer i-1)
     // ---- side stream: part A of layer i+1 (channels [0, cin), final once layer i-1 has published its statistics) ----
-    if (raw && i > 0 && (rc = add_batch(bst, bst + g.ctot, L.bn1, cin - GROWTH, cin, at<float>(ws, W.bn1), cin, false))) return rc;   // layer i's newest 48 channels (sums final since layer i-1)
     if (pipelined && i + 1 < layers) {
-      RDM_HIP_OK(hipStreamWaitEvent(side, n.ev_fs[(i + 1) & 1], 0));                 // recorded at the end of layer i-1
-      if ((rc = launch_zero_rows(at<float>(ws, n.lws[b][i + 1].Y), 1, (long)g.M * g.cb, (long)g.M * g.cb, side))) return rc;
-      if ((rc = finalize_norm1(n, b, i + 1, 0, cin, true, ws, T, training, side))) return rc;
-      if ((rc = conv1_range(n, b, i + 1, 0, cin, true, false, ws, T, side))) return rc;
-      RDM_HIP_OK(hipEventRecord(n.ev_fa[(i + 1) & 1], side));
+      const LayerView Vn = layer_view(n, b, i + 1, ws, T);
+      RDM_HIP_OK(hipStreamWaitEvent(side, n.ev[EV_FS + ((i + 1) & 1)], 0));                 // recorded at the end of layer i-1
+      if ((rc = launch_zero_rows(Vn.Y, 1, (long)g.M * g.cb, (long)g.M * g.cb, side))) return rc;
+      if ((rc = finalize_norm1(Vn, 0, cin, true, training, side))) return rc;
+      if ((rc = conv1_range(n, b, i + 1, Vn, 0, cin, true, false, ws, side))) return rc;
+      RDM_HIP_OK(hipEventRecord(n.ev[EV_FA + ((i + 1) & 1)], side));
     }
     // ---- main: conv1 of layer i ----
     const bool fuse = training && fuse_stats(g.M, g.cb);
     bool stats_done = false;
     if (pipelined && i > 0) {
-      if (!raw && (rc = finalize_norm1(n, b, i, cin - GROWTH, cin, false, ws, T, training, s))) return rc;
-      RDM_HIP_OK(hipStreamWaitEvent(s, n.ev_fa[i & 1], 0));
+      if (!raw && (rc = finalize_norm1(V, c48, cin, false, training, s))) return rc;
+      RDM_HIP_OK(hipStreamWaitEvent(s, n.ev[EV_FA + (i & 1)], 0));
       if (training) {
         // part B is three K-slabs and runs unsplit: its epilogue adds part A's finished sum, stores the final value and takes
         // the channel statistics of it - no separate reduction pass over Y on the critical path (it took 56 us beside part A)
-        if ((rc = conv1_range(n, b, i, cin - GROWTH, cin, false, true, ws, T, s, true, raw))) return rc;
+        if ((rc = conv1_range(n, b, i, V, c48, cin, false, true, ws, s, true, raw))) return rc;
         stats_done = true;
-      } else if ((rc = conv1_range(n, b, i, cin - GROWTH, cin, true, false, ws, T, s))) return rc;
+      } else if ((rc = conv1_range(n, b, i, V, c48, cin, true, false, ws, s))) return rc;
     } else {
-      if ((rc = finalize_norm1(n, b, i, 0, cin, true, ws, T, training, s))) return rc;
-      if ((rc = conv1_range(n, b, i, 0, cin, false, fuse, ws, T, s))) return rc;
+      if ((rc = finalize_norm1(V, 0, cin, true, training, s))) return rc;
+      if ((rc = conv1_range(n, b, i, V, 0, cin, false, fuse, ws, s))) return rc;
     }
-    if (training && !fuse && !stats_done && (rc = launch_colstats(Y, g.cb, g.M, g.cb, sty, sty + g.cb, s))) return rc;
+    if (training && !fuse && !stats_done && (rc = launch_colstats(V.Y, g.cb, g.M, g.cb, V.statY.sum, V.statY.sq, s))) return rc;
     if (raw) {                                                          // norm2: the 3x3 conv forms the affine itself; bookkeeping batched (below)
-      if (i > 0 && (rc = add_batch(at<double>(ws, n.lws[b][i - 1].statY), at<double>(ws, n.lws[b][i - 1].statY) + g.cb, reg().layers[b][i - 1].bn2, 0, g.cb,
-                                   at<float>(ws, n.lws[b][i - 1].bn2), g.cb, true)))
-        return rc;                                                      // layer i-1's sums became final one layer ago: no wait for the flush
-    } else if ((rc = launch_bn_finalize(sty, sty + g.cb, (double)g.M, F(T, L.bn2.w), F(T, L.bn2.b), F(T, L.bn2.rm), F(T, L.bn2.rv),
-                                        static_cast<long long*>(T[L.bn2.nbt]), bn2, bn2 + g.cb, bn2 + 2 * g.cb, bn2 + 3 * g.cb, g.cb, training, s)))
-      return rc;
-    const float* w2p = n.opt_packed3x3 ? F(T, L.conv2) : at<float>(ws, W.w2p);     // else packed on the side stream at the start of forward
-    if (b == 0 && i == 0) RDM_HIP_OK(hipStreamWaitEvent(s, n.ev_side, 0));
-    FwdArgs c{};
-    c.g = geom3x3(n.B, g.H, g.W, 1);
-    c.A = Y; c.lda = g.cb; c.C = g.cb; c.a_scale = bn2; c.a_shift = bn2 + g.cb;
-    c.Wt = w2p; c.wtap = (long)GROWTH * g.cb; c.ldw = g.cb;
-    c.out = blk + cin; c.ldc = g.ctot; c.M = g.M; c.N = GROWTH;
-    c.stat0 = bst + cin; c.stat1 = bst + g.ctot + cin;
+      if (i > 0 && (rc = add_norm2(i - 1))) return rc;                  // layer i-1's sums became final one layer ago: no wait for the flush
+    } else if ((rc = launch_bn_finalize(V.statY, (double)g.M, V.p2, V.bn2, g.cb, training, s))) return rc;
+    if (b == 0 && i == 0) RDM_HIP_OK(hipStreamWaitEvent(s, n.ev[EV_SIDE], 0));     // the 3x3 weight images are packed on the side stream at the start of forward
+    FwdArgs c = conv2_fwd_args(V);
     if (raw) {
       c.a_scale = nullptr; c.a_shift = nullptr;
-      c.a_sum = sty; c.a_sq = sty + g.cb; c.a_gamma = F(T, L.bn2.w); c.a_beta = F(T, L.bn2.b); c.a_count = (double)g.M;
+      c.a_sum = V.statY.sum; c.a_sq = V.statY.sq; c.a_gamma = V.p2.gamma; c.a_beta = V.p2.beta; c.a_count = (double)g.M;
       c.accumulate = 1;                                                 // the slice was zeroed with the whole block at its start
       if (n.opt_fuse_stats3 && cdiv(g.M, 128) <= 128) c.tickets = at<unsigned>(ws, n.tickets);      // the last K split of a pixel tile takes the tile's statistics
     }
     if (R.wino) {
       // Winograd F(2x2, 3x3): the ordered reduction of the split partials also takes the channel statistics (no zero fill, no separate pass)
-      WinoConv wv{};
-      wv.A = Y; wv.lda = g.cb; wv.C = g.cb; wv.a_scale = bn2; wv.a_shift = bn2 + g.cb; wv.U = at<float>(ws, n.winoU[b][i]);
-      wv.out = blk + cin; wv.ldc = g.ctot; wv.N = GROWTH; wv.B = n.B; wv.H = g.H; wv.W = g.W;
-      wv.x6 = R.wino_x6;
+      WinoConv wv = conv2_wino_args(V);
+      wv.U = at<float>(ws, n.winoU[b][i]); wv.x6 = R.wino_x6;
       wv.split = wv.x6 ? n.wino_split_x6[b] : 0; wv.partial = at<float>(ws, n.winoPartial); wv.partial_floats = n.winoPartialFloats;
-      if (training) { wv.stat0 = bst + cin; wv.stat1 = bst + g.ctot + cin; }
+      if (training) { wv.stat0 = V.ost.sum; wv.stat1 = V.ost.sq; }
       if ((rc = launch_conv3x3_wino_fwd(wv, s))) return rc;
     } else {
       const bool fuse2 = training && fuse_stats(g.M, GROWTH);
       if ((rc = launch_conv_fwd(c, false, fuse2 ? EPI_STORE_STATS : EPI_STORE, s)) < 0) return rc;
-      if (training && !fuse2 && c.tickets == nullptr && (rc = launch_colstats(blk + cin, g.ctot, g.M, GROWTH, bst + cin, bst + g.ctot + cin, s))) return rc;
+      if (training && !fuse2 && c.tickets == nullptr && (rc = launch_colstats(V.out, g.ctot, g.M, GROWTH, V.ost.sum, V.ost.sq, s))) return rc;
     }
-    if (pipelined) RDM_HIP_OK(hipEventRecord(n.ev_fs[i & 1], s));     // layer i's output channels + their statistics are final
+    if (pipelined) RDM_HIP_OK(hipEventRecord(n.ev[EV_FS + (i & 1)], s));     // layer i's output channels + their statistics are final
   }
-  if (raw) {                                                            // the last layer's norm2, then whatever is left in the batch
-    const int i = layers - 1;
-    if ((rc = add_batch(at<double>(ws, n.lws[b][i].statY), at<double>(ws, n.lws[b][i].statY) + g.cb, reg().layers[b][i].bn2, 0, g.cb, at<float>(ws, n.lws[b][i].bn2), g.cb, true)))
-      return rc;
-    if ((rc = flush_batch())) return rc;
-  }
+  if (raw && ((rc = add_norm2(layers - 1)) || (rc = flush_batch()))) return rc;      // the last layer's norm2, then whatever is left in the batch
   return 0;
 }
 
@@ -686,27 +751,24 @@ int forward_transition(NetImpl& n, int t, void* ws, void* const* T, int training
   const BlockGeom& gn = n.bg[t + 1];
   const int C = kTrans[t].cin, Co = kTrans[t].cout;
   float* blk = at<float>(ws, n.blk[t]);
-  double* bst = at<double>(ws, n.blkstat[t]);
-  float* bn = at<float>(ws, n.transBn[t]);
-  const BnIdx& b = reg().trans_bn[t];
+  const StatPair bst(at<double>(ws, n.blkstat[t]), g.ctot), nst(at<double>(ws, n.blkstat[t + 1]), gn.ctot);
+  const BnAffine bn(at<float>(ws, n.transBn[t]), C);
   // statistics over the zero-PADDED tensor (pad_br precedes the BatchNorm, RDM_Net.py:532)
   const double count = (double)n.B * (g.H + 1) * (g.W + 1);
-  int rc = launch_bn_finalize(bst, bst + g.ctot, count, F(T, b.w), F(T, b.b), F(T, b.rm), F(T, b.rv), static_cast<long long*>(T[b.nbt]), bn,
-                              bn + C, bn + 2 * C, bn + 3 * C, C, training, s);
+  int rc = launch_bn_finalize(bst, count, BnParams(T, reg().trans_bn[t]), bn, C, training, s);
   if (rc) return rc;
   float* P = at<float>(ws, n.transP[t]);
-  if ((rc = launch_trans_pool(blk, g.ctot, bn, bn + C, P, n.B, g.H, g.W, C, s))) return rc;
+  if ((rc = launch_trans_pool(blk, g.ctot, bn.scale, bn.shift, P, n.B, g.H, g.W, C, s))) return rc;
   float* nblk = at<float>(ws, n.blk[t + 1]);
-  double* nst = at<double>(ws, n.blkstat[t + 1]);
   FwdArgs a{};
   a.g = geom1x1(n.B, gn.H, gn.W);
   a.A = P; a.lda = C; a.C = C;
   a.Wt = F(T, reg().trans_conv[t]); a.wtap = 0; a.ldw = C;
   a.out = nblk; a.ldc = gn.ctot; a.M = gn.M; a.N = Co;
-  a.stat0 = nst; a.stat1 = nst + gn.ctot;
+  a.stat0 = nst.sum; a.stat1 = nst.sq;
   const bool fuse = training && fuse_stats(gn.M, Co);
   if ((rc = launch_conv_fwd(a, false, fuse ? EPI_STORE_STATS : EPI_STORE, s)) < 0) return rc;
-  if (training && !fuse && (rc = launch_colstats(nblk, gn.ctot, gn.M, Co, nst, nst + gn.ctot, s))) return rc;
+  if (training && !fuse && (rc = launch_colstats(nblk, gn.ctot, gn.M, Co, nst.sum, nst.sq, s))) return rc;
   return 0;
 }
 
@@ -718,7 +780,6 @@ int zero_f32(float* p, size_t n, hipStream_t s) {
 int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, void* const* T, void* const* Gr, hipStream_t s) {
   const BlockGeom& g = n.bg[b];
   const int training = n.training_saved;
-  float* blk = at<float>(ws, n.blk[b]);
   float* G = at<float>(ws, n.G[b]);
   float* dZ1 = at<float>(ws, n.dZ1);
   int rc;
@@ -727,28 +788,20 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
   const BlockRoute& R = route(n, b);
   for (int i = i_hi; i >= i_lo; --i) {
     const LayerIdx& L = reg().layers[b][i];
-    const LayerWs& W = n.lws[b][i];
+    const LayerView V = layer_view(n, b, i, ws, T, Gr);
     const LayerRoute& r = R.layer[i];
     const Encodings& enc = r.enc[Gr[L.conv1] != nullptr];
-    const int cin = kBlocks[b].cin + i * GROWTH, cb = g.cb;
-    const int par = i & 1;
+    const int cin = V.cin, cb = V.cb, par = i & 1;
     float* dZ = at<float>(ws, n.dZ[par]);
-    float* Y = at<float>(ws, W.Y);
-    float* bn1 = at<float>(ws, W.bn1);
-    float* bn2 = at<float>(ws, W.bn2);
-    const float* w2p = n.opt_packed3x3 ? F(T, L.conv2) : at<float>(ws, W.w2p);
     const float* go = G + cin;
     // the layer's output gradient `go` is final here (all later layers have accumulated into it)
-    RDM_HIP_OK(hipEventRecord(n.ev_go, s));
+    RDM_HIP_OK(hipEventRecord(n.ev[EV_GO], s));
     // ---- side stream: conv2 (3x3) wgrad ----
     if (Gr[L.conv2]) {
       // packed gradients go straight to the caller's tensor; otherwise into a scratch that is unpacked to OIHW afterwards
-      float* dW3 = n.opt_packed3x3 ? F(Gr, L.conv2) : at<float>(ws, W.dw3);
-      RDM_HIP_OK(hipStreamWaitEvent(side, n.ev_go, 0));
-      WgradArgs w{};
-      w.g = geom3x3(n.B, g.H, g.W, 1);
-      w.G = go; w.ldg = g.ctot; w.N = GROWTH; w.Xs = Y; w.ldx = cb; w.C = cb; w.x_scale = bn2; w.x_shift = bn2 + cb;
-      w.dW = dW3; w.wtap = (long)GROWTH * cb; w.ldw = cb;
+      float* dW3 = n.opt_packed3x3 ? F(Gr, L.conv2) : at<float>(ws, n.lws[b][i].dw3);
+      RDM_HIP_OK(hipStreamWaitEvent(side, n.ev[EV_GO], 0));
+      WgradArgs w = conv2_wgrad_args(V, go, dW3);
       // the split-precision and the direct kernel accumulate with f32 atomics into the zeroed gradient
       if (r.wg3 != Wg3::WINO && !(n.opt_packed3x3 && n.opt_prezeroed) && (rc = zero_f32(dW3, 9 * (size_t)GROWTH * cb, side))) return rc;
       if (r.wg3 == Wg3::XS) {
@@ -763,25 +816,15 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
         if ((rc = launch_xs_wgrad3x3(w, side))) return rc;
       } else if (r.wg3 == Wg3::WINO) {
         // Winograd F(3x3, 2x2): writes the gradient (ordered split reduction, no atomics, no zero fill)
-        WinoWgrad wv{};
-        wv.G = go; wv.ldg = g.ctot; wv.N = GROWTH; wv.A = Y; wv.lda = cb; wv.C = cb; wv.a_scale = bn2; wv.a_shift = bn2 + cb;
-        wv.dW = dW3; wv.wtap = (long)GROWTH * cb; wv.ldw = cb;
+        WinoWgrad wv = conv2_wino_wgrad_args(V, go, dW3);
         wv.Vy = at<float>(ws, n.winoVy); wv.vy_floats = n.winoVyFloats; wv.part = at<float>(ws, n.winoQ); wv.part_floats = n.winoQFloats;
-        wv.B = n.B; wv.H = g.H; wv.W = g.W;
         if ((rc = launch_conv3x3_wino_wgrad(wv, side))) return rc;
       } else if ((rc = launch_conv_wgrad(w, side))) return rc;
       if (!n.opt_packed3x3 && (rc = launch_unpack_w(dW3, F(Gr, L.conv2), GROWTH, cb, 9, GROWTH, side))) return rc;
     }
     // ---- main: conv2 dgrad -> dZ[par], gated by relu2, with the norm2 backward reductions ----
-    if (n.dz_busy[par]) { RDM_HIP_OK(hipStreamWaitEvent(s, n.ev_dz[par], 0)); n.dz_busy[par] = false; }   // side wgrad still reading this buffer?
-    double* s0 = at<double>(ws, W.bs2);
-    double* s1 = s0 + cb;
-    FwdArgs d{};
-    d.g = geom3x3(n.B, g.H, g.W, -1);
-    d.A = go; d.lda = g.ctot; d.C = GROWTH;
-    d.Wt = w2p; d.wtap = (long)GROWTH * cb; d.ldw = cb;
-    d.out = dZ; d.ldc = cb; d.M = g.M; d.N = cb;
-    d.stat0 = s0; d.stat1 = s1; d.X = Y; d.ldx = cb; d.x_scale = bn2; d.x_shift = bn2 + cb;
+    if (n.dz_busy[par]) { RDM_HIP_OK(hipStreamWaitEvent(s, n.ev[EV_DZ + par], 0)); n.dz_busy[par] = false; }   // side wgrad still reading this buffer?
+    FwdArgs d = conv2_dgrad_args(V, go, dZ);
     d.out_bf16 = enc.dz_bf16;
     if (r.dg3_xs) {
       const bool pk = n.pk_bwd_valid && !n.xsP3[b].empty();
@@ -789,44 +832,31 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
     } else if ((rc = launch_conv_fwd(d, true, EPI_MASK_STATS, s)) < 0) return rc;      // split-K layers gate + reduce atomically
     // one elementwise pass dZ := dY (BN-backward coefficients computed in the same kernel).  Forming dY inside the conv1
     // dgrad / wgrad loaders instead was measured slower (heavier loaders cost the MFMA kernels more: 155 vs 164 img/s)
-    if ((rc = launch_bn_bwd_apply(dZ, cb, dZ, cb, Y, cb, s0, s1, (double)g.M, F(T, L.bn2.w), bn2 + 2 * cb, bn2 + 3 * cb,
-                                  Gr[L.bn2.w] ? F(Gr, L.bn2.w) : nullptr, Gr[L.bn2.b] ? F(Gr, L.bn2.b) : nullptr, g.M, cb, false, training, s, enc.dz_bf16, enc.dy_split)))
-      return rc;
+    if ((rc = launch_bn_bwd_apply(dZ, cb, dZ, cb, V.Y, cb, V.bs2, (double)g.M, V.p2, V.bn2, V.d2, g.M, cb, false, training, s, enc.dz_bf16, enc.dy_split))) return rc;
     // ---- side stream: conv1 (1x1) wgrad straight into the PyTorch-layout gradient ([cb][cin][1][1]) ----
     if (Gr[L.conv1]) {
       // (round 3: moving this launch to the caller's stream for the last 1-4 layers of dense_e2 / e3 - where the side stream has become the
       // longer one, 25.9 vs 22.3 ms of kernel time - changed nothing: 72.0-72.7 vs 72.2 ms; the step is throughput-bound, not balance-bound)
-      RDM_HIP_OK(hipEventRecord(n.ev_dy, s));
-      RDM_HIP_OK(hipStreamWaitEvent(side, n.ev_dy, 0));
+      RDM_HIP_OK(hipEventRecord(n.ev[EV_DY], s));
+      RDM_HIP_OK(hipStreamWaitEvent(side, n.ev[EV_DY], 0));
       if (!n.opt_prezeroed && (rc = zero_f32(F(Gr, L.conv1), (size_t)cb * cin, side))) return rc;
-      WgradArgs w{};
-      w.g = geom1x1(n.B, g.H, g.W);
-      w.G = dZ; w.ldg = cb; w.N = cb;
-      w.Xs = blk; w.ldx = g.ctot; w.C = cin; w.x_scale = bn1; w.x_shift = bn1 + cin;
-      w.dW = F(Gr, L.conv1); w.wtap = 0; w.ldw = cin;
+      WgradArgs w = conv1_wgrad_args(V, dZ, F(Gr, L.conv1));
       w.g_bf16 = enc.dz_bf16;
       w.g_split = enc.dy_split;
       if (enc.xh_split) {
         // relu1(norm1(x)) of this layer, activated and split ONCE (the GEMM re-stages its activation tile for each of its cb / 128 gradient tiles)
         float* xh = at<float>(ws, n.xsXh);
-        if ((rc = launch_split_rows(blk, g.ctot, bn1, bn1 + cin, xh, cin, g.M, cin, side))) return rc;
+        if ((rc = launch_split_rows(V.blk, g.ctot, V.bn1.scale, V.bn1.shift, xh, cin, g.M, cin, side))) return rc;
         w.Xs = xh; w.ldx = cin; w.x_scale = nullptr; w.x_shift = nullptr; w.x_split = 1;
       }
       if (r.wg1_xs) { w.xsplit = r.np; rc = launch_xs_wgrad1x1(w, side); }
       else rc = launch_conv_wgrad(w, side);
       if (rc) return rc;
-      RDM_HIP_OK(hipEventRecord(n.ev_dz[par], side));
+      RDM_HIP_OK(hipEventRecord(n.ev[EV_DZ + par], side));
       n.dz_busy[par] = true;
     }
     // ---- main: conv1 dgrad -> dZ1, gated by relu1, with the norm1 backward reductions ----
-    s0 = at<double>(ws, W.bs1);
-    s1 = s0 + cin;
-    FwdArgs e{};
-    e.g = geom1x1(n.B, g.H, g.W);
-    e.A = dZ; e.lda = cb; e.C = cb;
-    e.Wt = F(T, L.conv1); e.wtap = 0; e.ldw = cin;
-    e.out = dZ1; e.ldc = cin; e.M = g.M; e.N = cin;
-    e.stat0 = s0; e.stat1 = s1; e.X = blk; e.ldx = g.ctot; e.x_scale = bn1; e.x_shift = bn1 + cin;
+    FwdArgs e = conv1_dgrad_args(V, dZ, dZ1);
     e.a_bf16 = enc.dz_bf16;
     e.a_split = enc.dy_split;
     const bool defer = R.defer;                                           // deferred norm1 backward: decided once per BLOCK
@@ -843,21 +873,18 @@ int backward_block(NetImpl& n, int b, int i_hi, int i_lo, bool join, void* ws, v
       float* b_out = bc + (size_t)(i & 1) * 2 * n.deferLd;
       if (i == kBlocks[b].layers - 1 && (rc = zero_f32(b_in, (size_t)2 * n.deferLd, s))) return rc;
       const int sc0 = i > 0 ? cin - GROWTH : 0, sn = i > 0 ? GROWTH : cin;
-      if ((rc = launch_bn_bwd_defer(G, g.ctot, blk, g.ctot, s0, s1, (double)g.M, F(T, L.bn1.w), bn1 + 2 * cin, bn1 + 3 * cin,
-                                    Gr[L.bn1.w] ? F(Gr, L.bn1.w) : nullptr, Gr[L.bn1.b] ? F(Gr, L.bn1.b) : nullptr, b_in, b_in + n.deferLd, b_out,
-                                    b_out + n.deferLd, g.M, cin, sc0, sn, training, s)))
+      if ((rc = launch_bn_bwd_defer(G, g.ctot, V.blk, g.ctot, V.bs1, (double)g.M, V.p1, V.bn1, V.d1, b_in, b_in + n.deferLd, b_out, b_out + n.deferLd, g.M, cin, sc0, sn,
+                                    training, s)))
         return rc;
-    } else if ((rc = launch_bn_bwd_apply(G, g.ctot, dZ1, cin, blk, g.ctot, s0, s1, (double)g.M, F(T, L.bn1.w), bn1 + 2 * cin, bn1 + 3 * cin,
-                                         Gr[L.bn1.w] ? F(Gr, L.bn1.w) : nullptr, Gr[L.bn1.b] ? F(Gr, L.bn1.b) : nullptr, g.M, cin, true, training, s)))
-      return rc;
+    } else if ((rc = launch_bn_bwd_apply(G, g.ctot, dZ1, cin, V.blk, g.ctot, V.bs1, (double)g.M, V.p1, V.bn1, V.d1, g.M, cin, true, training, s))) return rc;
   }
   // join: everything the side stream produced (weight gradients) is ordered before what the caller enqueues next.  A caller that
   // consumes gradients stage by stage (the data-parallel exchange) needs it after every stage; without one it is needed once per
   // segment only (RDM_NET_OPT_JOIN_PER_SEGMENT) and the dgrad chain of the next stage starts without draining the wgrad stream -
   // the dZ double buffers stay fenced by their own events (dz_busy) across stages
   if (join) {
-    RDM_HIP_OK(hipEventRecord(n.ev_side, side));
-    RDM_HIP_OK(hipStreamWaitEvent(s, n.ev_side, 0));
+    RDM_HIP_OK(hipEventRecord(n.ev[EV_SIDE], side));
+    RDM_HIP_OK(hipStreamWaitEvent(s, n.ev[EV_SIDE], 0));
     n.dz_busy[0] = n.dz_busy[1] = false;
   }
   return 0;
@@ -872,10 +899,9 @@ int backward_transition(NetImpl& n, int t, void* ws, void* const* T, void* const
   float* Gn = at<float>(ws, n.G[t + 1]);      // gradient wrt the transition output = first Co channels
   float* G = at<float>(ws, n.G[t]);
   float* P = at<float>(ws, n.transP[t]);
-  float* bn = at<float>(ws, n.transBn[t]);
+  const BnAffine bn(at<float>(ws, n.transBn[t]), C);
   float* dP = at<float>(ws, n.dP);
-  double* s0 = at<double>(ws, n.transBs[t]);
-  double* s1 = s0 + C;
+  const StatPair bs(at<double>(ws, n.transBs[t]), C);
   float* cA = at<float>(ws, n.cA); float* cB = at<float>(ws, n.cB); float* cC = at<float>(ws, n.cC);
   const BnIdx& b = reg().trans_bn[t];
   const int wi = reg().trans_conv[t];
@@ -895,12 +921,10 @@ int backward_transition(NetImpl& n, int t, void* ws, void* const* T, void* const
   d.Wt = F(T, wi); d.wtap = 0; d.ldw = C;
   d.out = dP; d.ldc = C; d.M = gn.M; d.N = C;
   if ((rc = launch_conv_fwd(d, true, EPI_STORE, s)) < 0) return rc;
-  if ((rc = launch_trans_pool_bwd_reduce(dP, blk, g.ctot, bn, bn + C, n.B, g.H, g.W, C, s0, s1, s))) return rc;
+  if ((rc = launch_trans_pool_bwd_reduce(dP, blk, g.ctot, bn.scale, bn.shift, n.B, g.H, g.W, C, bs.sum, bs.sq, s))) return rc;
   const double count = (double)n.B * (g.H + 1) * (g.W + 1);
-  if ((rc = launch_bn_bwd_coeffs(s0, s1, count, F(T, b.w), bn + 2 * C, bn + 3 * C, cA, cB, cC, Gr[b.w] ? F(Gr, b.w) : nullptr,
-                                 Gr[b.b] ? F(Gr, b.b) : nullptr, C, training, s)))
-    return rc;
-  return launch_trans_pool_bwd_apply(dP, blk, g.ctot, bn, bn + C, cA, cB, cC, G, g.ctot, n.B, g.H, g.W, C, s);
+  if ((rc = launch_bn_bwd_coeffs(bs, count, BnParams(T, b), bn, cA, cB, cC, BnGrads(Gr, b), C, training, s))) return rc;
+  return launch_trans_pool_bwd_apply(dP, blk, g.ctot, bn.scale, bn.shift, cA, cB, cC, G, g.ctot, n.B, g.H, g.W, C, s);
 }
 
 }  // namespace
@@ -949,21 +973,18 @@ int dense_block_bf16_train(const DenseBf16TrainBlock& d, hipStream_t s) {
   const double count = (double)d.M;
   for (int i = 0; i < d.layers; ++i) {
     const int cin = d.cin0 + i * GROWTH;
-    float* a1 = d.aff1;                                              // scale | shift | mean | rstd of [0, cin), row stride cin
-    if ((rc = launch_bn_finalize(d.bsum, d.bsq, count, d.g1[i], d.b1[i], d.rm1[i], d.rv1[i], d.nbt1[i], a1, a1 + cin, a1 + 2 * cin, a1 + 3 * cin, cin, 1, s)))
-      return rc;
+    const BnAffine a1(d.aff1, cin), a2(d.aff2, d.cb);                // the records of [0, cin) / of the bottleneck, reused by every layer
+    if ((rc = launch_bn_finalize(StatPair(d.bsum, d.bsq), count, d.p1[i], a1, cin, 1, s))) return rc;
     GemmBf16Args a{};
-    a.X = d.blk; a.ldx = d.ctot; a.K = cin; a.scale = a1; a.shift = a1 + cin;
+    a.X = d.blk; a.ldx = d.ctot; a.K = cin; a.scale = a1.scale; a.shift = a1.shift;
     a.W = d.w1[i]; a.ldw = cin;
     a.out = d.Y; a.ldc = d.cb; a.M = d.M; a.N = d.cb;
     a.partial = d.partial; a.partial_floats = d.partial_floats;
     a.osum = d.ysum; a.osq = d.ysq; a.stats = d.stats; a.stats_floats = d.stats_floats;
     if ((rc = launch_gemm_bf16(a, false, s))) return rc;
-    float* a2 = d.aff2;
-    if ((rc = launch_bn_finalize(d.ysum, d.ysq, count, d.g2[i], d.b2[i], d.rm2[i], d.rv2[i], d.nbt2[i], a2, a2 + d.cb, a2 + 2 * d.cb, a2 + 3 * d.cb, d.cb, 1, s)))
-      return rc;
+    if ((rc = launch_bn_finalize(StatPair(d.ysum, d.ysq), count, d.p2[i], a2, d.cb, 1, s))) return rc;
     Conv3Bf16Args c{};
-    c.Y = d.Y; c.ldy = d.cb; c.C = d.cb; c.scale = a2; c.shift = a2 + d.cb;
+    c.Y = d.Y; c.ldy = d.cb; c.C = d.cb; c.scale = a2.scale; c.shift = a2.shift;
     c.Wt = d.w3[i]; c.wtap = (long)GROWTH * d.cb; c.ldw = d.cb;
     c.out = d.blk + cin; c.ldc = d.ctot; c.B = d.B; c.H = d.H; c.W = d.W; c.M = d.M;
     c.partial = d.partial; c.partial_floats = d.partial_floats;
@@ -1041,7 +1062,7 @@ int rdm_net_buffer(const rdm_net* net, const char* name, int64_t* offset_bytes, 
   if (sscanf(name, "blk%d", &b) == 1 && b >= 0 && b < 4) { *offset_bytes = n.blk[b]; *numel = (int64_t)n.bg[b].M * n.bg[b].ctot; return RDM_OK; }
   if (sscanf(name, "G%d", &b) == 1 && b >= 0 && b < 4) { *offset_bytes = n.G[b]; *numel = (int64_t)n.bg[b].M * n.bg[b].ctot; return RDM_OK; }
   if (sscanf(name, "Y%d_%d", &b, &i) == 2 && b >= 0 && b < 4 && i >= 0 && i < kBlocks[b].layers) { *offset_bytes = n.lws[b][i].Y; *numel = (int64_t)n.bg[b].M * n.bg[b].cb; return RDM_OK; }
-  if (sscanf(name, "bn1_%d_%d", &b, &i) == 2 && b >= 0 && b < 4 && i >= 0 && i < kBlocks[b].layers) { *offset_bytes = n.lws[b][i].bn1; *numel = 4 * (int64_t)(kBlocks[b].cin + i * GROWTH); return RDM_OK; }
+  if (sscanf(name, "bn1_%d_%d", &b, &i) == 2 && b >= 0 && b < 4 && i >= 0 && i < kBlocks[b].layers) { *offset_bytes = n.lws[b][i].bn1; *numel = 4 * (int64_t)layer_cin(b, i); return RDM_OK; }
   if (sscanf(name, "bn2_%d_%d", &b, &i) == 2 && b >= 0 && b < 4 && i >= 0 && i < kBlocks[b].layers) { *offset_bytes = n.lws[b][i].bn2; *numel = 4 * (int64_t)n.bg[b].cb; return RDM_OK; }
   if (sscanf(name, "P%d", &b) == 1 && b >= 0 && b < 3) { *offset_bytes = n.transP[b]; *numel = (int64_t)n.bg[b + 1].M * kTrans[b].cin; return RDM_OK; }
   if (!strcmp(name, "logits")) { *offset_bytes = n.logits; *numel = (int64_t)n.bg[3].M * 192; return RDM_OK; }
@@ -1082,7 +1103,7 @@ double rdm_net_forward_flops(const rdm_net* net) {
   double mac = (double)n->M1 * 96 * 147;
   for (int b = 0; b < 4; ++b)
     for (int i = 0; i < kBlocks[b].layers; ++i)
-      mac += (double)n->bg[b].M * n->bg[b].cb * (kBlocks[b].cin + i * GROWTH) + (double)n->bg[b].M * GROWTH * n->bg[b].cb * 9;
+      mac += (double)n->bg[b].M * n->bg[b].cb * layer_cin(b, i) + (double)n->bg[b].M * GROWTH * n->bg[b].cb * 9;
   for (int t = 0; t < 3; ++t)   // algorithmic count: the reference convolves at the padded full resolution
     mac += (double)n->B * (n->bg[t].H + 1) * (n->bg[t].W + 1) * kTrans[t].cin * kTrans[t].cout;
   mac += (double)n->bg[3].M * 180 * 2208;
@@ -1112,43 +1133,44 @@ int rdm_net_forward(rdm_net* net, const float* x, void* const* T, void* ws, size
   // library's side stream, fenced against the caller's stream on both ends
   // (with RDM_NET_OPT_PACKED_3X3 the caller keeps them packed and these 78 launches do not exist)
   if ((rc = n.ensure_side())) return rc;
-  RDM_HIP_OK(hipEventRecord(n.ev_go, s));
-  RDM_HIP_OK(hipStreamWaitEvent(n.side, n.ev_go, 0));
+  RDM_HIP_OK(hipEventRecord(n.ev[EV_GO], s));
+  RDM_HIP_OK(hipStreamWaitEvent(n.side, n.ev[EV_GO], 0));
   // split kernels: the three-way-split images of the conv1 weights the forward reads first (dense_e2's first layer starts ~0.3 ms from here)
   n.pk_fwd_valid = n.pk_bwd_valid = false;
   if (n.opt_prepack && n.opt_split_fwd && !n.opt_det) {
     for (int b = 0; b < 4; ++b)
       if (route(n, b).xf && !n.xfP[b].empty())
         for (int i = 0; i < kBlocks[b].layers; ++i) {
-          const int cin = kBlocks[b].cin + i * GROWTH;
-          if ((rc = launch_xs_pack_w1_fwd(F(T, reg().layers[b][i].conv1), cin, n.bg[b].cb, cin, at<unsigned char>(ws, n.xfP[b][i]), n.side))) return rc;
+          const LayerView V = layer_view(n, b, i, ws, T);
+          if ((rc = launch_xs_pack_w1_fwd(V.w1, V.cin, V.cb, V.cin, at<unsigned char>(ws, n.xfP[b][i]), n.side))) return rc;
         }
-    RDM_HIP_OK(hipEventRecord(n.ev_pkf, n.side));
+    RDM_HIP_OK(hipEventRecord(n.ev[EV_PKF], n.side));
     n.pk_fwd_valid = true;
   }
   if (!n.opt_packed3x3)
     for (int b = 0; b < 4; ++b)
-      for (int i = 0; i < kBlocks[b].layers; ++i)
-        if ((rc = launch_pack_w(F(T, reg().layers[b][i].conv2), at<float>(ws, n.lws[b][i].w2p), GROWTH, n.bg[b].cb, 9, GROWTH, n.side))) return rc;
+      for (int i = 0; i < kBlocks[b].layers; ++i) {
+        const LayerView V = layer_view(n, b, i, ws, T);
+        if ((rc = launch_pack_w(V.w2, V.w2p, GROWTH, V.cb, 9, GROWTH, n.side))) return rc;
+      }
   for (int b = 0; b < 4; ++b)                                 // Winograd weight transforms U = G g G^T, off the critical path like the packing
     if (route(n, b).wino)
       for (int i = 0; i < kBlocks[b].layers; ++i) {
-        const float* w2p = n.opt_packed3x3 ? F(T, reg().layers[b][i].conv2) : at<float>(ws, n.lws[b][i].w2p);
-        if ((rc = launch_wino_weight(w2p, (long)GROWTH * n.bg[b].cb, n.bg[b].cb, GROWTH, n.bg[b].cb, at<float>(ws, n.winoU[b][i]), n.side, route(n, b).wino_x6))) return rc;
+        const LayerView V = layer_view(n, b, i, ws, T);
+        if ((rc = launch_wino_weight(V.w2p, (long)GROWTH * V.cb, V.cb, GROWTH, V.cb, at<float>(ws, n.winoU[b][i]), n.side, route(n, b).wino_x6))) return rc;
       }
-  RDM_HIP_OK(hipEventRecord(n.ev_side, n.side));
+  RDM_HIP_OK(hipEventRecord(n.ev[EV_SIDE], n.side));
   // ... and, behind everything the forward waits for, the split / fragment-order images the BACKWARD's input-gradient kernels read (the weights
   // do not change between this forward and its backward): 108 launches that used to sit on the backward's dependent chain
   if (training && n.opt_prepack && n.opt_split_bwd && !n.opt_det) {
     for (int b = 3; b >= 0; --b)
       if (route(n, b).xs && !n.xsP3[b].empty())
         for (int i = kBlocks[b].layers - 1; i >= 0; --i) {
-          const int cin = kBlocks[b].cin + i * GROWTH, cb = n.bg[b].cb;
-          const float* w2p = n.opt_packed3x3 ? F(T, reg().layers[b][i].conv2) : at<float>(ws, n.lws[b][i].w2p);
-          if ((rc = launch_xs_pack_w3_dgrad(w2p, (long)GROWTH * cb, cb, cb, at<unsigned char>(ws, n.xsP3[b][i]), n.side))) return rc;
-          if ((rc = launch_xs_pack_w1_dgrad(F(T, reg().layers[b][i].conv1), cin, cb, cin, at<unsigned char>(ws, n.xsP1[b][i]), n.side))) return rc;
+          const LayerView V = layer_view(n, b, i, ws, T);
+          if ((rc = launch_xs_pack_w3_dgrad(V.w2p, (long)GROWTH * V.cb, V.cb, V.cb, at<unsigned char>(ws, n.xsP3[b][i]), n.side))) return rc;
+          if ((rc = launch_xs_pack_w1_dgrad(V.w1, V.cin, V.cb, V.cin, at<unsigned char>(ws, n.xsP1[b][i]), n.side))) return rc;
         }
-    RDM_HIP_OK(hipEventRecord(n.ev_pkb, n.side));
+    RDM_HIP_OK(hipEventRecord(n.ev[EV_PKB], n.side));
     n.pk_bwd_valid = true;
   }
   // stem: 7x7/s2 conv as im2col + GEMM (K = 147 padded to 160), bias, then 3x3/s2 max-pool
@@ -1205,15 +1227,14 @@ int rdm_net_bf16_prepare(rdm_net* net, void* const* T, void* wbuf, size_t wbuf_b
   hipStream_t s = stream;
   int rc;
   auto affine = [&](const BnIdx& b, size_t off, int C, int Cp) {      // eval-mode BatchNorm folded to (scale, shift): running statistics; arrays Cp long
-    float* d = at<float>(wbuf, off);
-    return launch_bn_finalize(nullptr, nullptr, 1.0, F(T, b.w), F(T, b.b), F(T, b.rm), F(T, b.rv), nullptr, d, d + Cp, d + 2 * Cp, d + 3 * Cp, C, 0, s);
+    return launch_bn_finalize(StatPair(), 1.0, BnParams(T, b, false), BnAffine(at<float>(wbuf, off), Cp), C, 0, s);
   };
   RDM_HIP_OK(hipMemsetAsync(wbuf, 0, n.bf_wtotal, s));        // the padded rows / columns / affines of the bottleneck widths are zeros
   for (int b = 0; b < 4; ++b)
     for (int i = 0; i < kBlocks[b].layers; ++i) {
       const LayerIdx& L = reg().layers[b][i];
       const NetImpl::Bf16Layer& W = n.bfl[b][i];
-      const int cin = kBlocks[b].cin + i * GROWTH, cb = n.bg[b].cb, cbp = n.bf_cbp[b];
+      const int cin = layer_cin(b, i), cb = n.bg[b].cb, cbp = n.bf_cbp[b];
       if ((rc = launch_f32_to_bf16_rows(F(T, L.conv1), cin, at<char>(wbuf, W.w1), cin, cb, cin, cin, s))) return rc;
       if (n.bf_act3[b]) { if ((rc = launch_pack_w3_frag_bf16(F(T, L.conv2), at<char>(wbuf, W.w3), cb, cbp, n.opt_packed3x3, s))) return rc; }
       else if (n.opt_packed3x3) { if ((rc = launch_f32_to_bf16_rows(F(T, L.conv2), cb, at<char>(wbuf, W.w3), cbp, 9L * GROWTH, cb, cb, s))) return rc; }
@@ -1367,7 +1388,7 @@ static int backward_stem(NetImpl& n, void* ws, void* const* T, void* const* Gr, 
 static int backward_stage(NetImpl& n, int stage, const float* dlogits, void* ws, void* const* T, void* const* Gr, hipStream_t s) {
   const Registry::Stage& st = reg().stages[stage];
   int rc;
-  if (stage == 0 && n.pk_bwd_valid) RDM_HIP_OK(hipStreamWaitEvent(s, n.ev_pkb, 0));      // the packed weights of the input-gradient kernels (long done)
+  if (stage == 0 && n.pk_bwd_valid) RDM_HIP_OK(hipStreamWaitEvent(s, n.ev[EV_PKB], 0));      // the packed weights of the input-gradient kernels (long done)
   if (st.first_of_seg) {
     if (st.seg == 0) { if ((rc = backward_head(n, dlogits, ws, T, Gr, s))) return rc; }
     else if ((rc = backward_transition(n, st.block, ws, T, Gr, s))) return rc;          // seg 1 -> trans_e4 (t = 2) feeding dense_e4 (b = 2), ...

@@ -500,12 +500,9 @@ int rdm_rel_bf16_prepare(int32_t id, void* const* T, void* wbuf, size_t wbuf_byt
     const int b = 12 * i, cin = kCin0 + i * kGrowth;
     if ((rc = launch_f32_to_bf16_rows(Fp(T, b + 5), cin, at<char>(wbuf, P.dw1[i]), cin, kCb, cin, cin, s))) return rc;
     if ((rc = launch_pack_w_bf16(Fp(T, b + 11), at<char>(wbuf, P.dw3[i]), kGrowth, kCb, kCb, 9, s))) return rc;
-    float* d1 = at<float>(wbuf, P.dbn1[i]);
-    if ((rc = launch_bn_finalize(nullptr, nullptr, 1.0, Fp(T, b), Fp(T, b + 1), const_cast<float*>(Fp(T, b + 2)), const_cast<float*>(Fp(T, b + 3)), nullptr,
-                                 d1, d1 + cin, d1 + 2 * cin, d1 + 3 * cin, cin, 0, s))) return rc;
-    float* d2 = at<float>(wbuf, P.dbn2[i]);
-    if ((rc = launch_bn_finalize(nullptr, nullptr, 1.0, Fp(T, b + 6), Fp(T, b + 7), const_cast<float*>(Fp(T, b + 8)), const_cast<float*>(Fp(T, b + 9)), nullptr,
-                                 d2, d2 + kCb, d2 + 2 * kCb, d2 + 3 * kCb, kCb, 0, s))) return rc;
+    // eval-mode affines of norm1 (tensors b .. b + 4) and norm2 (b + 6 .. b + 10): no sums, no batch counted
+    if ((rc = launch_bn_finalize(StatPair(), 1.0, BnParams(T, BnIdx{b, b + 1, b + 2, b + 3, b + 4}, false), BnAffine(at<float>(wbuf, P.dbn1[i]), cin), cin, 0, s))) return rc;
+    if ((rc = launch_bn_finalize(StatPair(), 1.0, BnParams(T, BnIdx{b + 6, b + 7, b + 8, b + 9, b + 10}, false), BnAffine(at<float>(wbuf, P.dbn2[i]), kCb), kCb, 0, s))) return rc;
   }
   auto bias = [&](size_t off, int idx, int n) -> int {
     RDM_HIP_OK(hipMemcpyAsync(at<char>(wbuf, off), T[idx], (size_t)n * 4, hipMemcpyDeviceToDevice, s));
@@ -617,10 +614,7 @@ int rdm_rel_forward_bf16_train(int32_t id, const void* enc, int32_t ld_enc, cons
     for (int i = 0; i < kLayers; ++i) {
       const int b = 12 * i;                                          // norm1 w b rm rv nbt, conv1, norm2 w b rm rv nbt, conv2
       d.w1[i] = at<char>(wb, P.dw1[i]); d.w3[i] = at<char>(wb, P.dw3[i]);
-      d.g1[i] = Fp(T, b); d.b1[i] = Fp(T, b + 1); d.rm1[i] = static_cast<float*>(T[b + 2]); d.rv1[i] = static_cast<float*>(T[b + 3]);
-      d.nbt1[i] = static_cast<long long*>(T[b + 4]);
-      d.g2[i] = Fp(T, b + 6); d.b2[i] = Fp(T, b + 7); d.rm2[i] = static_cast<float*>(T[b + 8]); d.rv2[i] = static_cast<float*>(T[b + 9]);
-      d.nbt2[i] = static_cast<long long*>(T[b + 10]);
+      d.p1[i] = BnParams(T, BnIdx{b, b + 1, b + 2, b + 3, b + 4}); d.p2[i] = BnParams(T, BnIdx{b + 6, b + 7, b + 8, b + 9, b + 10});
     }
     if ((rc = dense_block_bf16_train(d, s))) return rc;
   }
