@@ -210,6 +210,12 @@ HEADERS = {
         "rdm_depth_anchor_field": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, f64, f64, vp, vp, vp, vp]),
         "rdm_depth_frames_corrected": (C.c_int, [vp, vp, i32, vp, C.POINTER(f64), i32, i32, i32, C.POINTER(f64), i32, f64, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
     },
+    # include/rdm_fuse.h: multi-frame depth fusion (frames with poses integrated into one TSDF volume in one launch, the volume's zero crossings as oriented points in rdm_cloud.h's records), part of librdm_hip.so, declared in a header of its own
+    "rdm_fuse.h": {
+        "rdm_tsdf_integrate": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(f64), vp, i32, f64, f64, f64, f64, i32, i32, i32, C.POINTER(f64), vp, vp, vp, vp]),
+        "rdm_tsdf_extract_workspace_bytes": (sz, [i32, i32, i32]),
+        "rdm_tsdf_extract": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(f64), f64, i32, vp, i64, vp, vp, sz, vp]),
+    },
     # librdm_bench.so (include/rdm_bench.h): measurement kernels of tools/ and bench_ops.py - not part of the product
     "rdm_bench.h": {
         "rdm_microbench_copy": (C.c_int, [vp, vp, i64, vp]),

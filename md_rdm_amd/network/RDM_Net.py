@@ -865,6 +865,19 @@ class DepthEstimationNet(BaseModel):
         return warp.render(planes["f32"], intrinsics, pose, rgb=rgb, out_hw=out_hw, intrinsics_out=intrinsics_out, min_depth=min_depth, max_depth=max_depth,
                            splat=splat, fill=fill, want=want)
 
+    def predict_fused(self, x, frame_hw, intrinsics, poses, volume, view=None, rgb=None, flip=False, refine=None, min_depth=0.0, max_depth=math.inf,
+                      weight=1.0, **kwargs):
+        """The predicted frames integrated into a ``fuse.Volume``: ONE ``predict_metric`` call (its float32 plane; ``kwargs`` and ``refine`` as for
+        ``predict_cloud``, so ``anchors`` / ``anchor`` tie the frames to measurements first) followed by ``volume.integrate`` of that plane under
+        ``poses`` (WORLD -> camera, one or one per sample), with ``intrinsics`` = (fx, fy, cx, cy) of the (h, w) frame and ``rgb`` (B,h,w,3) uint8
+        as its colours.  The result is the float32 plane that went into the volume."""
+        on = not (refine is None or refine is False)
+        if on and rgb is None:
+            raise _lib.RdmError("predict_fused: refine needs rgb, the guide of the filter")
+        planes = self.predict_metric(x, frame_hw, view=view, flip=flip, want=("f32",), refine=refine, guide=rgb if on else None, **kwargs)
+        volume.integrate(planes["f32"], intrinsics, poses, rgb=rgb, min_depth=min_depth, max_depth=max_depth, weight=weight)
+        return planes["f32"]
+
     # ---- the reference forward (RDM_Net.py:70-135) -----------------------------------------
     def forward(self, x):
         bf16 = self.precision == "bf16"

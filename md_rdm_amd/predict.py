@@ -75,6 +75,20 @@ F (``median`` makes a prior that outliers do not move).  ``--min_depth`` / ``--m
 points: their effect on real data has not been measured.
 
   python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --anchors frame0_lidar.png --anchor_fit median --anchor_reject 0.5 frame0.npy
+
+``--fuse --poses FILE`` (with --metric --native; for ``--synthetic`` inputs with --full_res) also writes ONE ``fused.ply`` for the whole sequence
+(md_rdm_amd.fuse): every batch's saved frames and their colours are integrated into one truncated signed distance volume (one launch per batch),
+and after the last batch the volume's surface is read out as oriented, coloured points in world coordinates (three more launches, twice).  ``FILE``
+is a ``.npy`` or a text file with one row of twelve values r00 r01 r02 t0 r10 .. t2 per input frame, in input order: the pose [R | t] from WORLD to
+that frame's camera, or with ``--poses_c2w`` from the camera to the world (what SLAM systems write; inverted on the host in float64).  The volume
+has voxels of ``--fuse_voxel`` metres (default 0.02) and a truncation of ``--fuse_trunc`` metres (default 4 voxels); ``--fuse_origin X Y Z`` and
+``--fuse_dims NX NY NZ`` place it, and what is not given comes from the box of the cameras' frusta up to ``--max_depth`` (``fuse.bounds``), which
+must then be given.  A voxel counts once its weight reaches ``--fuse_min_weight`` (default 1: one frame); ``--fuse_max_weight`` caps the running
+weight (default 64).  ``--camera`` / ``--intrinsics`` and ``--min_depth`` / ``--max_depth`` are --ply's; ``--ply_normals`` gives the points
+normals; with ``--anchors`` the anchored frames and with ``--refine`` the refined ones are fused - unanchored monocular frames disagree in scale and
+blur the surface.  The defaults are starting points: their effect on real data has not been measured.
+
+  python -m md_rdm_amd.predict --checkpoint last.ckpt --out maps --metric --native --anchors a0.png a1.png --fuse --poses poses.txt --poses_c2w --max_depth 6 f0.npy f1.npy
 """
 import os
 import sys
@@ -142,6 +156,19 @@ def build_parser():
     p.add_argument("--anchor_reject", type=float, default=None, metavar="F", help="--anchors: drop anchors whose log residual against the prior exceeds F (default: none)")
     p.add_argument("--anchor_unit", type=float, default=None, metavar="M", help="--anchors: metres per step of a 16-bit PNG anchor file (default 0.001)")
     p.add_argument("--anchor_no_field", action="store_true", help="--anchors: fit the scale only, no correction field")
+    p.add_argument("--fuse", action="store_true", help="--metric, with --native or --synthetic --full_res: integrate every saved frame into one TSDF volume and write "
+                   "fused.ply, its surface as oriented points in world coordinates; needs --poses")
+    p.add_argument("--poses", type=str, default=None, metavar="FILE", help="--fuse: .npy or text, one row of twelve values r00 r01 r02 t0 .. t2 per input frame: world -> camera")
+    p.add_argument("--poses_c2w", action="store_true", help="--fuse: the rows of --poses are camera -> world and are inverted")
+    p.add_argument("--fuse_voxel", type=float, default=None, metavar="M", help="--fuse: the voxels' side in metres (default 0.02, a starting point: its effect on real "
+                   "data has not been measured)")
+    p.add_argument("--fuse_trunc", type=float, default=None, metavar="M", help="--fuse: the truncation distance in metres (default 4 voxels, a starting point, not measured)")
+    p.add_argument("--fuse_dims", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="--fuse: the volume's voxels (default: the box of the frusta up to --max_depth)")
+    p.add_argument("--fuse_origin", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="--fuse: the centre of voxel (0, 0, 0) in world metres (default: the "
+                   "box of the frusta up to --max_depth)")
+    p.add_argument("--fuse_min_weight", type=float, default=None, metavar="W", help="--fuse: a voxel counts from this weight on (default 1: seen by one frame; a starting "
+                   "point, not measured)")
+    p.add_argument("--fuse_max_weight", type=float, default=None, metavar="W", help="--fuse: the cap of a voxel's running weight, >= 1 (default 64)")
     return p
 
 
@@ -177,8 +204,10 @@ def check_ply_args(args):
     import math
     view = args.stereo is not None or args.view_pose is not None          # the novel views take the camera and the depth range too
     anchored = args.anchors is not None                                   # ... and the anchors the depth range
+    if args.fuse:                                                         # ... and the fused volume both, and --ply_normals for its points
+        view = anchored = True
     if not args.ply:
-        given = [f for f, v in (("--ply_normals", args.ply_normals), ("--ply_step", args.ply_step is not None), ("--camera", args.camera is not None and not view),
+        given = [f for f, v in (("--ply_normals", args.ply_normals and not args.fuse), ("--ply_step", args.ply_step is not None), ("--camera", args.camera is not None and not view),
                                 ("--intrinsics", args.intrinsics is not None and not view), ("--min_depth", args.min_depth is not None and not view and not anchored),
                                 ("--max_depth", args.max_depth is not None and not view and not anchored)) if v]
         if given:
@@ -284,6 +313,83 @@ def check_anchor_args(args):
         raise SystemExit("md_rdm_amd.predict: --anchors: " + bad)
 
 
+def load_poses(path):
+    """(N,12) float64 rows of a .npy ((N,12), (N,3,4) or (N,4,4)) or of a text file with twelve values per row"""
+    import numpy as np
+    try:
+        p = np.load(path) if os.path.splitext(path)[1].lower() == ".npy" else np.loadtxt(path, dtype=np.float64, ndmin=2)
+        p = np.asarray(p, np.float64)
+    except (OSError, ValueError) as e:
+        raise SystemExit("md_rdm_amd.predict: --poses %s: %s" % (path, e))
+    if p.ndim == 3 and p.shape[1:] in ((3, 4), (4, 4)):
+        p = p[:, :3, :].reshape(-1, 12)
+    if p.ndim != 2 or p.shape[1] != 12 or not np.isfinite(p).all():
+        raise SystemExit("md_rdm_amd.predict: --poses %s: need rows of twelve finite values [R | t], got an array of shape %s" % (path, p.shape))
+    return np.ascontiguousarray(p)
+
+
+def check_fuse_args(args):
+    """the --fuse flags' own rules (the ranges are the library's, include/rdm_fuse.h); raises SystemExit.  -> the (N,12) world-to-camera poses, or None"""
+    import math
+    if not args.fuse:
+        given = [f for f, v in (("--poses", args.poses is not None), ("--poses_c2w", args.poses_c2w), ("--fuse_voxel", args.fuse_voxel is not None),
+                                ("--fuse_trunc", args.fuse_trunc is not None), ("--fuse_dims", args.fuse_dims is not None), ("--fuse_origin", args.fuse_origin is not None),
+                                ("--fuse_min_weight", args.fuse_min_weight is not None), ("--fuse_max_weight", args.fuse_max_weight is not None)) if v]
+        if given:
+            raise SystemExit("md_rdm_amd.predict: --poses, --poses_c2w, --fuse_voxel, --fuse_trunc, --fuse_dims, --fuse_origin, --fuse_min_weight and --fuse_max_weight "
+                             "need --fuse (got %s)" % " ".join(given))
+        return None
+    if not args.metric:
+        raise SystemExit("md_rdm_amd.predict: --fuse needs --metric: a volume is made of depth in metres")
+    if not (args.native or (args.synthetic and args.full_res)):
+        raise SystemExit("md_rdm_amd.predict: --fuse needs the colours of the saved frame and its camera: --native for file inputs, --full_res for --synthetic "
+                         "inputs (the frame is then the network input itself)")
+    if args.poses is None:
+        raise SystemExit("md_rdm_amd.predict: --fuse needs --poses FILE: one world-to-camera pose per input frame")
+    for flag, v in (("--fuse_voxel", args.fuse_voxel), ("--fuse_trunc", args.fuse_trunc)):
+        if v is not None and not (math.isfinite(v) and v > 0):
+            raise SystemExit("md_rdm_amd.predict: %s must be finite and > 0 (got %r)" % (flag, v))
+    if args.fuse_dims is not None and not (min(args.fuse_dims) > 0 and args.fuse_dims[0] * args.fuse_dims[1] * args.fuse_dims[2] <= 2 ** 31 - 1):
+        raise SystemExit("md_rdm_amd.predict: --fuse_dims must be three positive integers with a product of at most 2^31 - 1 (got %r)" % (args.fuse_dims,))
+    if args.fuse_origin is not None and not all(math.isfinite(v) for v in args.fuse_origin):
+        raise SystemExit("md_rdm_amd.predict: --fuse_origin must be three finite values (got %r)" % (args.fuse_origin,))
+    if args.fuse_min_weight is not None and math.isnan(args.fuse_min_weight):
+        raise SystemExit("md_rdm_amd.predict: --fuse_min_weight must not be NaN")
+    if args.fuse_max_weight is not None and not args.fuse_max_weight >= 1:
+        raise SystemExit("md_rdm_amd.predict: --fuse_max_weight must be >= 1, the weight of one frame (got %r)" % args.fuse_max_weight)
+    if (args.fuse_dims is None or args.fuse_origin is None) and args.max_depth is None:
+        raise SystemExit("md_rdm_amd.predict: --fuse sizes its volume from the cameras' frusta up to --max_depth: give --max_depth, or --fuse_dims and --fuse_origin")
+    poses = load_poses(args.poses)
+    n_in = args.synthetic or len(args.inputs)
+    if len(poses) != n_in:
+        raise SystemExit("md_rdm_amd.predict: --poses takes one row per input frame (got %d rows for %d inputs)" % (len(poses), n_in))
+    if args.poses_c2w:
+        from .fuse import pose_inverse
+        poses = pose_inverse(poses.reshape(-1, 3, 4)).reshape(-1, 12)
+    return poses
+
+
+def fuse_volume(args, poses, frames, intr_of, dev):
+    """the ``fuse.Volume`` of --fuse: ``frames`` the distinct saved-frame shapes, ``intr_of(frame)`` their intrinsics.  Origin and dims are
+    ``fuse.bounds``' over all the frames' frusta where they are not given; dims alone: the voxels from the given origin to that box's far corner."""
+    import math
+    from . import fuse
+    from ._lib import RdmError
+    voxel = args.fuse_voxel if args.fuse_voxel is not None else fuse.VOXEL
+    origin, dims = args.fuse_origin, args.fuse_dims
+    try:
+        if origin is None or dims is None:
+            boxes = [fuse.bounds(f, intr_of(f), poses.reshape(-1, 3, 4), args.max_depth, voxel) for f in frames]
+            lo = [min(o[a] for o, _ in boxes) for a in range(3)]
+            hi = [max(o[a] + (d[a] - 1) * voxel for o, d in boxes) for a in range(3)]
+            origin = lo if origin is None else origin
+            dims = [max(1, math.ceil((hi[a] - origin[a]) / voxel) + 1) for a in range(3)] if dims is None else dims
+        return fuse.Volume(dims, origin, voxel, trunc=args.fuse_trunc, color=True, max_weight=args.fuse_max_weight if args.fuse_max_weight is not None else fuse.MAX_WEIGHT,
+                           device=dev)
+    except RdmError as e:
+        raise SystemExit("md_rdm_amd.predict: --fuse: %s" % e)
+
+
 def anchor_options(args):
     """--anchor* -> the ``anchor`` argument of predict_metric"""
     opts = {k: v for k, v in (("fit", args.anchor_fit), ("cell", args.anchor_cell), ("sigma", args.anchor_sigma), ("lam", args.anchor_lambda), ("reject", args.anchor_reject),
@@ -378,6 +484,7 @@ def main(argv=None):
     check_mesh_args(args)
     check_view_args(args)
     check_anchor_args(args)
+    fuse_poses = check_fuse_args(args)
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -408,6 +515,11 @@ def main(argv=None):
     else:
         items = [(os.path.splitext(os.path.basename(p))[0], load_frame(p)) for p in args.inputs]
     pre = nyu.NyuGpuPreprocessor(resize=500, output_size=size, device=dev)
+    volume = None
+    if args.fuse:                                                # the saved frames are raw frames (--native) or the network input (--synthetic --full_res)
+        raw_intr = cloud.intrinsics_params(args.intrinsics if args.intrinsics is not None else args.camera or "nyu")
+        volume = fuse_volume(args, fuse_poses, sorted({tuple(a.shape[:2]) for _, a in items}) if args.native else [size],
+                             lambda f: raw_intr if args.native else cloud.intrinsics_in_view(raw_intr, (0.0, 0.0) + size, f), dev)
     seen, i = {}, 0
     while i < len(items):
         j = i + 1
@@ -445,13 +557,16 @@ def main(argv=None):
             maps = planes["f32"].unsqueeze(1)
             steps = planes["u16"].cpu().numpy() if args.png16 else None
             views = view_jobs(args)
-            if args.ply or views:
+            if args.ply or views or args.fuse:
                 intr = cloud.intrinsics_params(args.intrinsics if args.intrinsics is not None else args.camera or "nyu")
                 if not args.native:                                  # the saved frame shows a rectangle of the raw frame (all of the network input for --synthetic)
                     intr = cloud.intrinsics_in_view(intr, (0.0, 0.0) + tuple(size) if args.synthetic else nyu.test_view(batch.shape[1:3]), frame)
             rendered = []
-            if views:                                                # --synthetic --full_res: the frame is the network input, whose values in [0, 1) are the colours
+            if views or args.fuse:                                   # --synthetic --full_res: the frame is the network input, whose values in [0, 1) are the colours
                 colours = rgb if args.native else (x.permute(0, 2, 3, 1) * 255.0).clamp(0.0, 255.0).to(torch.uint8).contiguous()
+                if args.fuse:
+                    volume.integrate(planes["f32"], intr, fuse_poses[i:j].reshape(-1, 3, 4), rgb=colours, min_depth=args.min_depth or 0.0,
+                                     max_depth=args.max_depth if args.max_depth is not None else float("inf"))
                 for suffix, pose in views:
                     r = warp.render(planes["f32"], intr, pose, rgb=colours, min_depth=args.min_depth or 0.0, max_depth=args.max_depth if args.max_depth is not None else float("inf"),
                                     splat=args.view_splat if args.view_splat is not None else warp.SPLAT, fill=args.view_fill if args.view_fill is not None else warp.FILL,
@@ -493,6 +608,11 @@ def main(argv=None):
                 cloud.write_ply(stem + ".ply", records[n], ply_counts[n], args.ply_normals, args.native)
         print("batch of %d: %.1f images/s" % (j - i, (j - i) / dt), flush=True)
         i = j
+    if args.fuse:
+        from . import fuse
+        path = os.path.join(args.out, "fused.ply")
+        n = volume.write_ply(path, normals=args.ply_normals, min_weight=args.fuse_min_weight if args.fuse_min_weight is not None else fuse.MIN_WEIGHT)
+        print("fused %d frames into %d x %d x %d voxels of %g m: %d surface points in %s" % ((len(items),) + tuple(volume.dims) + (volume.voxel, n, path)), flush=True)
     return 0
 
 
